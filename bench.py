@@ -25,7 +25,15 @@ Process forms at N > 1:
             all-reduces from one host thread, synch/common.c:14-54): --gpus N
             without a torch.distributed.run environment, or --single-process.
 
-Run:  python bench.py [--gpus N --steps K --warmup W]
+A plain run sets up, warms up, times the K steps and prints the line (value,
+ms_per_step, the roofline of the kernels as they ran in the timed steps).
+--full adds, after the timed region, every measurement that takes runs of its
+own: the replica optimiser step, the sma.c seam, the copy ceiling, the
+host-staged step and the CPU baselines at N = 1; the host's idle-GPU enqueue
+time, the host-staged step and the separate RCCL tuning-log run at N > 1.
+--dump-outputs DIR writes what the last timed step left for its caller.
+
+Run:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
       python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
       python bench.py --gpus N [--single-process]
 """
@@ -79,6 +87,16 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=50)
     p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed region, also run every further measurement, each in runs of its own: the "
+                        "replica optimiser step, the sma.c seam, the copy ceiling, the host-staged step and the CPU "
+                        "baselines at N = 1; the host's idle-GPU enqueue time, the host-staged step and the separate "
+                        "RCCL tuning-log run at N > 1 (the --no-* options below drop single ones).  Without it the "
+                        "run sets up, warms up, times the steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last of them left for the caller (each GPU's base "
+                        "model z and momentum `last`, each replica's corrected w) as DIR/<name>.npy, float32, at most "
+                        "64 MB in all (beyond that the same seeded sample of elements from every array)")
     p.add_argument("--model", choices=["resnet50", "lenet"], default="resnet50")
     p.add_argument("--replicas", type=int, default=8, help="replicas per GPU")
     p.add_argument("--alpha", type=float, default=0.1)
@@ -633,6 +651,57 @@ def state_max_abs(gpu, world):
             top = max(top, float(np.max(np.abs(a))) if a.size else 0.0)
     from crossbow_amd import dist as D
     return D.max_over_ranks(top, world)
+
+
+DUMP_BYTES = 60_000_000  # --dump-outputs: every array of the run together (under 64 MB with the .npy headers)
+DUMP_EDGE = 4096        # elements at each end of an array that a sample always holds
+
+
+def dump_indices(n: int, arrays: int):
+    """The elements --dump-outputs keeps of every array: None (all of them)
+    while `arrays` whole fp32 arrays fit DUMP_BYTES, else the same sorted
+    sample for every array and every run: both ends of the buffer (where the
+    kernels' tails and the first workgroup run) and indices drawn from SEED."""
+    import numpy as np
+    per = DUMP_BYTES // (4 * max(1, arrays))
+    if n <= per:
+        return None
+    edge = min(DUMP_EDGE, per // 4)
+    drawn = np.random.default_rng(SEED).integers(0, n, size=per - 2 * edge, dtype=np.int64)
+    return np.unique(np.concatenate([np.arange(edge, dtype=np.int64), np.arange(n - edge, n, dtype=np.int64), drawn]))
+
+
+def dump_outputs(gpu, directory: str, n: int, G: int, replicas: int, momentum: float) -> dict:
+    """--dump-outputs: what the timed path's last step left for its caller --
+    each local GPU's base model z and (with momentum) `last`, each local
+    replica's w, which the step corrects in place -- read back after the
+    timed region and written as float32 <name>.npy.  The inputs are
+    fill_synthetic(SEED) and the step count the arguments', so two builds run
+    with the same arguments write comparable files."""
+    import numpy as np
+    from crossbow_amd import BUF_DATA, BUF_LAST
+    m = 1 if momentum > 0 else 0
+    idx = dump_indices(n, G * (1 + m + replicas))
+    os.makedirs(directory, exist_ok=True)
+    gpu.wait()
+    written = []
+
+    def put(name, a):
+        a = np.ascontiguousarray(a if idx is None else a[idx], dtype=np.float32)
+        np.save(os.path.join(directory, name + ".npy"), a)
+        written.append(name)
+
+    for g in gpu.local_devices():
+        tag = "" if G == 1 else f"_gpu{g}"
+        put("z" + tag, gpu.base_read(g, BUF_DATA))
+        if m:
+            put("last" + tag, gpu.base_read(g, BUF_LAST))
+    for i in gpu.local_replicas():
+        put(f"w{i}", gpu.replica_read(i, BUF_DATA))
+    return {"directory": directory, "arrays": written, "dtype": "float32",
+            "elements_per_array": n if idx is None else int(idx.size),
+            "sample": None if idx is None else f"first and last {DUMP_EDGE} elements and indices drawn with "
+                                               f"numpy default_rng({SEED}), sorted, the same for every array"}
 
 
 def sma_dynamics(alpha: float, momentum: float, replicas_total: int) -> dict:
@@ -1267,6 +1336,13 @@ def main():
     fields = block_fields(gpu, D, args, world, n, G, nlocal, split, blk, chosen, tuning, calib,
                           args.rehearse_one_gpu)
     merge_block(result, fields)
+    if args.dump_outputs:
+        # before any later phase steps again: the state is the last timed step's.
+        # Before the line is published: a dump that cannot be written fails the run.
+        wd.enter("dump outputs", 300)
+        result["outputs"] = dump_outputs(gpu, args.dump_outputs, n, G, args.replicas, args.momentum)
+        if G > 1:
+            result["outputs"]["block"] = "the first timed block (the peer-read form's, if one follows, is not written)"
     # From here on the line exists: a later phase that misses its deadline
     # makes the watchdog print it (with `incomplete_phase`) instead of nothing.
     wd.publish(result, result_out)
@@ -1319,7 +1395,7 @@ def main():
             apply_config(gpu, reported, single)
         ar_algo = reported["algorithm"]
 
-        if G > 1:
+        if G > 1 and args.full:
             # Host side of the step (lockAny + synchronise + unlockAny, every local
             # device's enqueue) against the device's step: the single-process form
             # enqueues all G devices' kernels and collectives from one thread.
@@ -1353,9 +1429,11 @@ def main():
                 "collective of calibration, tuning and the timed region")
 
         step_bytes, _ = alg_bytes(n, args.replicas, args.momentum, 2 if split else 1)
-        if G > 1 and not args.no_staged and peer_only:
+        # every measurement below takes runs of its own: --full only
+        staged_leg = args.full and not args.no_staged
+        if G > 1 and staged_leg and peer_only:
             result["host_staged"] = {"skipped": "the host-staged step's collective is RCCL's, which refuses a repeated device"}
-        elif G > 1 and not args.no_staged:
+        elif G > 1 and staged_leg:
             # Host-staged rate at N > 1 (north_star: the path starts and ends in
             # host memory): each GPU's replicas live in its own pinned mirror and
             # cross its own PCIe link; zero-copy staging kernels, kernel A /
@@ -1388,18 +1466,18 @@ def main():
                     "per_gpu_GBs": round(step_bytes / (ms * 1e-3) / 1e9, 2),
                     "timed": "HIP events per device (staged step: host in, host and device out), max over devices"}}
 
-        if rank == 0 and G == 1 and not args.no_optimiser:
+        if rank == 0 and G == 1 and args.full and not args.no_optimiser:
             wd.enter("replica optimiser step", 120)
             result["replica_optimiser"] = bench_optimiser(gpu, torch, n, args)
-        if rank == 0 and G == 1 and not args.no_seam:
+        if rank == 0 and G == 1 and args.full and not args.no_seam:
             wd.enter("sma.c seam", 180)
             result["seam"] = bench_seam(torch, n, args)
 
-        if rank == 0 and G == 1:
+        if rank == 0 and G == 1 and args.full:
             if not args.no_copy_ceiling:
                 wd.enter("copy ceiling", 120)
                 result["copy_ceiling_GBs"] = round(gpu.bench_copy(1 << 30, 20), 1)
-            if not args.no_staged:
+            if staged_leg:
                 # Host-staged rate (north_star): pinned H2D of z, last, s_i, w_i,
                 # the step, pinned D2H of z, last, w_i.  Reported, never `value`.
                 wd.enter("host-staged step", 300)
@@ -1472,6 +1550,8 @@ def main():
                 entries, source = None, "no RCCL collective in the chosen form"
             elif args.no_rccl_tuning_run:
                 entries, source = None, "--no-rccl-tuning-run"
+            elif not args.full:
+                entries, source = None, "not run: the separate tuning-log run is part of --full"
             elif args.rehearse_one_gpu and not single and 2 * G + 2 > 16:
                 # the separate run's ranks would join this run's on the one GPU
                 entries, source = None, f"not run: a {G}-rank rehearsal plus {G} more ranks exceeds 16 processes on one GPU"

@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 out=gpurun_out/bisect
 mkdir -p "$out"
 trees=(. "$@")
-COMMON=(--steps 20 --warmup 5 --no-cpu-baseline --no-staged --no-seam --no-copy-ceiling --watchdog-scale 0)
+COMMON=(--full --steps 20 --warmup 5 --no-cpu-baseline --no-staged --no-seam --no-copy-ceiling --watchdog-scale 0)
 run() {  # tag tree extra...
   local tag=$1 tree=$2; shift 2
   echo "== $tag" >&2

@@ -9,7 +9,7 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 for N in ${RANKS:-2 4 8}; do
   timeout -k 10 ${SECS:-240} python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-    --master-port $((29600 + N)) bench.py --gpus $N --steps ${STEPS:-10} --warmup 3 --rehearse-one-gpu ${BENCH_ARGS:-} \
+    --master-port $((29600 + N)) bench.py --gpus $N --steps ${STEPS:-10} --warmup 3 --rehearse-one-gpu --full ${BENCH_ARGS:-} \
     > gpurun_out/rehearse_n$N.log 2>&1
   rc=$?
   echo "== N=$N rc=$rc"

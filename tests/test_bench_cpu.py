@@ -403,3 +403,54 @@ def test_identity_trusts_overflow_only_where_the_dynamics_predicts_it(monkeypatc
     idn = bench.block_identity(None, 1, None, chosen, 1, True, 1, None,
                                {"fresh_max_abs": 0.26, "steps_since_fresh": 1000}, bounded)
     assert not idn["dynamics"]["overflow_expected"] and not idn["trusted"]
+
+
+def test_dump_outputs_writes_a_fixed_sample_within_the_budget(tmp_path):
+    # --dump-outputs: z, last and every replica's w as float32 .npy; arrays
+    # that fit 64 MB together are written whole, larger ones as one sorted,
+    # seeded sample (both ends of the buffer always in it) that is the same
+    # for every array and every run.
+    import numpy as np
+
+    import bench
+    assert bench.dump_indices(1_111_946, 10) is None  # LeNet, 8 replicas: 44 MB, whole
+    n = 25_557_032  # ResNet-50: 10 arrays of 102 MB
+    idx = bench.dump_indices(n, 10)
+    assert np.array_equal(idx, bench.dump_indices(n, 10)) and np.all(np.diff(idx) > 0)
+    assert idx[0] == 0 and idx[-1] == n - 1 and idx.size > 1_000_000
+    assert np.array_equal(idx[:bench.DUMP_EDGE], np.arange(bench.DUMP_EDGE))
+    assert np.array_equal(idx[-bench.DUMP_EDGE:], np.arange(n - bench.DUMP_EDGE, n))
+
+    class FakeGpu:
+        def __init__(self, n):
+            self.n = n
+
+        def wait(self):
+            pass
+
+        def local_devices(self):
+            return [0]
+
+        def local_replicas(self):
+            return [0, 1]
+
+        def base_read(self, g, kind):
+            return np.arange(self.n, dtype=np.float32) + np.float32(0.5 * kind)
+
+        def replica_read(self, i, kind):
+            return -np.arange(self.n, dtype=np.float32) - np.float32(i)
+
+    small = bench.dump_outputs(FakeGpu(1000), str(tmp_path / "small"), 1000, 1, 2, 0.9)
+    assert small["arrays"] == ["z", "last", "w0", "w1"] and small["elements_per_array"] == 1000 and small["sample"] is None
+    assert sorted(os.listdir(tmp_path / "small")) == ["last.npy", "w0.npy", "w1.npy", "z.npy"]
+    w1 = np.load(tmp_path / "small" / "w1.npy")
+    assert w1.dtype == np.float32 and np.array_equal(w1, -np.arange(1000, dtype=np.float32) - 1)
+    assert bench.dump_outputs(FakeGpu(1000), str(tmp_path / "mu0"), 1000, 1, 2, 0.0)["arrays"] == ["z", "w0", "w1"]
+    n = 6_000_000  # 4 arrays of 24 MB: sampled
+    big = bench.dump_outputs(FakeGpu(n), str(tmp_path / "big"), n, 1, 2, 0.9)
+    idx = bench.dump_indices(n, 4)
+    assert big["elements_per_array"] == idx.size and "default_rng" in big["sample"]
+    z = np.load(tmp_path / "big" / "z.npy")
+    assert z.dtype == np.float32 and np.array_equal(z, idx.astype(np.float32))  # exact below 2^24
+    total = sum(os.path.getsize(tmp_path / "big" / f) for f in os.listdir(tmp_path / "big"))
+    assert total <= 64_000_000

@@ -48,7 +48,7 @@ def test_bench_one_gpu_prints_one_json_line():
 def test_bench_two_ranks_through_the_launcher_prints_one_json_line():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29671", "bench.py", "--gpus", "2",
-           "--rehearse-one-gpu", "--bucket-mb", "16"] + QUICK
+           "--rehearse-one-gpu", "--bucket-mb", "16", "--full"] + QUICK
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=280)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _one_line(p.stdout)
@@ -168,7 +168,7 @@ def test_bench_single_process_two_devices_one_gpu():
     """The reference's own multi-GPU topology: one process over N devices
     (cbx_init -> ncclCommInitAll), here two devices that are both device 0,
     so the all-reduce is the peer-read form (RCCL refuses a repeated device)."""
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--single-process", "--rehearse-one-gpu"] + QUICK
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--single-process", "--rehearse-one-gpu", "--full"] + QUICK
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=280)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _one_line(p.stdout)
@@ -213,10 +213,61 @@ def test_bench_two_ranks_host_staged_field():
     quick = [a for a in QUICK if a != "--no-staged"]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29673", "bench.py", "--gpus", "2",
-           "--rehearse-one-gpu", "--bucket-mb", "16"] + quick
+           "--rehearse-one-gpu", "--bucket-mb", "16", "--full"] + quick
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=280)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _one_line(p.stdout)
     _check(d, 2)
     z = d["host_staged"]["zerocopy"]
     assert z["step_ms"] > 0 and z["end_to_end_GBs"] > 0 and z["per_gpu_GBs"] > 0
+
+
+@pytest.mark.timeout(300)
+def test_plain_run_is_lean_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run times the steps and prints the line: none of the legs that
+    take runs of their own (--full) are in it.  --dump-outputs writes what the
+    last timed step left for the caller -- z, last and every replica's w --
+    bit for bit what the oracle computes in warm-up + timed steps from the
+    synthetic state this process fills with the same seed (so the inputs, and
+    with them the files, are the same from run to run).  LeNet: whole arrays."""
+    import numpy as np
+
+    from oracle import oracle as O
+    n, R, W, K = 1_111_946, 8, 1, 3
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", str(K), "--warmup", str(W), "--model", "lenet",
+           "--dump-outputs", str(tmp_path / "out")]
+    p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=140)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = _one_line(p.stdout)
+    _check(d, 1)
+    for key in ("replica_optimiser", "seam", "copy_ceiling_GBs", "host_staged", "cpu_baseline",
+                "cpu_baseline_multithread", "cpu_c1_lenet"):
+        assert key not in d, key
+    names = ["z", "last"] + [f"w{i}" for i in range(R)]
+    assert d["outputs"]["arrays"] == names and d["outputs"]["elements_per_array"] == n
+    assert sorted(os.listdir(tmp_path / "out")) == sorted(f"{k}.npy" for k in names)
+    got = {k: np.load(tmp_path / "out" / f"{k}.npy") for k in names}
+    assert sum(os.path.getsize(tmp_path / "out" / f"{k}.npy") for k in names) <= 64_000_000
+    # the inputs: the library's own synthetic state, as bench.py sets it up
+    from crossbow_amd import BUF_DATA, BUF_DIFF, BUF_LAST, SYNC_BSP, UPDATE_SMA, TheGPU
+    from crossbow_amd.variables import MODELS, register
+    g = TheGPU()
+    g.init([0])
+    try:
+        assert register(g, MODELS["lenet"]()) == n
+        g.setUpdateModelType(UPDATE_SMA)
+        g.setEamsgdAlpha(0.1)
+        g.setMomentum(0.9, 0)
+        g.setModelManager(R, SYNC_BSP)
+        g.fill_synthetic(O.SEED)
+        st = O.SmaState(1, R, n, 0.1, 0.9, [g.base_read(0, BUF_DATA)], [g.base_read(0, BUF_LAST)],
+                        [g.replica_read(i, BUF_DIFF) for i in range(R)],
+                        [g.replica_read(i, BUF_DATA) for i in range(R)])
+    finally:
+        g.free()
+    for _ in range(W + K):
+        O.sma_step(st)
+    want = dict([("z", st.z[0]), ("last", st.last[0])] + [(f"w{i}", st.w[i]) for i in range(R)])
+    for k, a in got.items():
+        assert a.dtype == np.float32 and a.shape == (n,)
+        assert np.array_equal(a.view(np.uint32), want[k].view(np.uint32)), f"{k} differs from the oracle"
