@@ -52,6 +52,20 @@ _IP = _c.POINTER(_c.c_int)
 _FP = _c.POINTER(_c.c_float)
 _CP = _c.c_char_p
 _UB = _c.POINTER(_c.c_ubyte)
+_LL = _c.c_longlong
+_LLP = _c.POINTER(_c.c_longlong)
+
+
+class BufferStats(_c.Structure):
+    """``cbx_buffer_stats``: 40 bytes, no implicit padding."""
+    _fields_ = [("sum", _c.c_double), ("sum_sq", _c.c_double), ("dist_sq", _c.c_double),
+                ("nonfinite", _c.c_ulonglong), ("max_abs", _c.c_float), ("reserved", _c.c_uint)]
+
+
+# The same layout as a numpy structured dtype (what TheGPU.modelStats returns).
+BUFFER_STATS_FIELDS = [("sum", "<f8"), ("sum_sq", "<f8"), ("dist_sq", "<f8"), ("nonfinite", "<u8"),
+                       ("max_abs", "<f4"), ("reserved", "<u4")]
+_BS = _c.POINTER(BufferStats)
 
 # name -> (restype, argtypes); mirrors include/crossbow_sma.h one to one.
 SIGNATURES = {
@@ -90,6 +104,11 @@ SIGNATURES = {
     "cbx_register_batchnorm_stats": (_I, [_P, _I, _I, _PP, _PP]),
     "cbx_add_model": (_I, [_P]),
     "cbx_del_model": (_I, [_P]),
+    "cbx_model_variable_count": (_I, [_P, _IP]),
+    "cbx_model_variable_info": (_I, [_P, _I, _IP, _IP, _LLP, _LLP]),
+    "cbx_model_stats": (_I, [_P, _I, _BS, _BS, _BS, _BS]),
+    "cbx_model_stats_last_ms": (_I, [_P, _I, _FP, _FP]),
+    "cbx_set_checkpoint_guard": (_I, [_P, _I]),
     "cbx_average_batchnorm_stats": (_I, [_P, _I, _IP, _PP, _PP, _IP]),
     "cbx_replica_lock": (_I, [_P, _I]),
     "cbx_replica_unlock": (_I, [_P, _I]),
@@ -151,6 +170,7 @@ SIGNATURES = {
     "cbx_sma_plan_free": (_I, [_P]),
     "cbx_sma_plan_set_buckets": (_I, [_P, _I]),
     "cbx_sma_plan_step": (_I, [_P, _PP, _PP, _PP, _I, _IP, _PP, _PP, _IP, _IP, _F, _F, _I]),
+    "cbx_sma_plan_buffer_stats": (_I, [_P, _I, _P, _P, _PP, _I, _LLP, _I, _BS, _BS, _BS, _BS]),
     "cbx_sma_optimise_buffers": (_I, [_P, _P, _P, _P, _P, _c.c_longlong, _F, _F, _F]),
     "cbx_sma_plan_average_batchnorm": (_I, [_P, _I, _IP, _PP, _PP, _IP]),
     "cbx_ssgd_plan_step": (_I, [_P, _PP, _PP, _PP, _PP, _I, _IP, _PP, _IP, _F, _I, _I]),

@@ -402,6 +402,21 @@ int cbx_set_model_manager(cbx_context *c, int replicas, int type) {
                 (long long)c->n);
   // model.c:116-120: `last` exists iff momentum > 0 (theModel's conf).
   c->has_last = m.conf.momentum > 0;
+  // The variables as cbx_model_stats sees them: in offset order, if they tile
+  // the n elements (every capacity its shape's bytes), else the whole model.
+  c->stats_vars.clear();
+  for (const auto &e : m.vars)
+    c->stats_vars.push_back({e.first.first, e.first.second, e.second.offset_bytes / 4, e.second.elements});
+  std::sort(c->stats_vars.begin(), c->stats_vars.end(),
+            [](const cbx_context::StatsVar &a, const cbx_context::StatsVar &b) { return a.offset < b.offset; });
+  long long at = 0;
+  bool tiled = !c->stats_vars.empty();
+  for (const auto &e : m.vars) tiled = tiled && e.second.offset_bytes % 4 == 0 && e.second.bytes == e.second.elements * 4;
+  for (const cbx_context::StatsVar &v : c->stats_vars) {
+    tiled = tiled && v.offset == at;
+    at += v.elements;
+  }
+  if (!tiled || at != c->n) c->stats_vars.assign(1, {-1, 0, 0, (long long)c->n});
   c->R = replicas;
   c->size = replicas * c->G;
   c->sync_type = type;
@@ -576,14 +591,126 @@ int cbx_unlock_any(cbx_context *c) {
   return count;
 }
 
+// ---- model statistics -------------------------------------------------------
+static int wait_streams(cbx_context *c);  // cbx_wait without the peer-read poison check
+
+int cbx_model_variable_count(cbx_context *c, int *count) {
+  TRY(check_manager_q(c));
+  if (!count) return fail(CBX_ERR_INVALID, "null variable count");
+  *count = (int)c->stats_vars.size();
+  return CBX_OK;
+}
+
+int cbx_model_variable_info(cbx_context *c, int v, int *op, int *order, long long *offset_elements,
+                            long long *elements) {
+  TRY(check_manager_q(c));
+  if (v < 0 || v >= (int)c->stats_vars.size())
+    return fail(CBX_ERR_INVALID, "variable %d out of range [0, %zu)", v, c->stats_vars.size());
+  const cbx_context::StatsVar &sv = c->stats_vars[v];
+  if (op) *op = sv.op;
+  if (order) *order = sv.order;
+  if (offset_elements) *offset_elements = sv.offset;
+  if (elements) *elements = sv.elements;
+  return CBX_OK;
+}
+
+// The reduction on local device d: its base `ref_kind` buffer against the
+// `buf_kind` buffer of each of its replicas, in id order.  totals / vars as
+// cbx::stats_run fills them (the reference first).
+static int device_stats(cbx_context *c, Device &d, int ref_kind, int buf_kind, std::vector<cbx_buffer_stats> &totals,
+                        std::vector<cbx_buffer_stats> *vars) {
+  const size_t V = c->stats_vars.size(), nb = d.replicas.size() + 1;
+  std::vector<long long> elems(V);
+  for (size_t v = 0; v < V; ++v) elems[v] = c->stats_vars[v].elements;
+  std::vector<const float *> bufs;
+  for (int id : d.replicas) bufs.push_back(replica_dev(d, *c->replicas[id], buf_kind));
+  totals.assign(nb, cbx_buffer_stats{});
+  if (vars) vars->assign(V * nb, cbx_buffer_stats{});
+  HIP_TRY(hipSetDevice(d.hip_id));
+  return cbx::stats_run(d.stats, d.stream, base_dev(c, d, ref_kind), bufs.data(), (int)bufs.size(), elems.data(),
+                        (int)V, c->n, totals.data(), vars ? vars->data() : nullptr);
+}
+
+int cbx_model_stats(cbx_context *c, int kind, cbx_buffer_stats *base, cbx_buffer_stats *replicas,
+                    cbx_buffer_stats *base_vars, cbx_buffer_stats *replica_vars) {
+  TraceRange trace("cbx_model_stats");
+  // It only reads model buffers and has returned before the next step is
+  // enqueued: no foreign op, the cross-step pipeline state stays valid.
+  TRY(check_manager_q(c));
+  if (kind != CBX_BUF_DATA && kind != CBX_BUF_DIFF)
+    return fail(CBX_ERR_INVALID, "cbx_model_stats: kind %d is neither CBX_BUF_DATA nor CBX_BUF_DIFF", kind);
+  if (!base || !replicas) return fail(CBX_ERR_INVALID, "cbx_model_stats: null result array");
+  TRY(wait_streams(c));
+  const size_t V = c->stats_vars.size();
+  const size_t size = (size_t)c->size.load();
+  std::fill(replicas, replicas + size, cbx_buffer_stats{});
+  if (replica_vars) std::fill(replica_vars, replica_vars + size * V, cbx_buffer_stats{});
+  std::vector<cbx_buffer_stats> totals, vars;
+  const bool want_vars = base_vars || replica_vars;
+  for (size_t k = 0; k < c->devs.size(); ++k) {
+    Device &d = c->devs[k];
+    TRY(device_stats(c, d, CBX_BUF_DATA, kind, totals, want_vars ? &vars : nullptr));
+    const size_t nb = d.replicas.size() + 1;
+    base[k] = totals[0];
+    for (size_t v = 0; base_vars && v < V; ++v) base_vars[k * V + v] = vars[v * nb];
+    for (size_t i = 0; i < d.replicas.size(); ++i) {
+      const size_t id = (size_t)d.replicas[i];
+      replicas[id] = totals[1 + i];
+      for (size_t v = 0; replica_vars && v < V; ++v) replica_vars[id * V + v] = vars[v * nb + 1 + i];
+    }
+  }
+  return CBX_OK;
+}
+
+int cbx_model_stats_last_ms(cbx_context *c, int local, float *pass_ms, float *total_ms) {
+  TRY(check_ctx_q(c));
+  if (local < 0 || local >= (int)c->devs.size() || !pass_ms || !total_ms)
+    return fail(CBX_ERR_INVALID, "bad statistics timing query");
+  HIP_TRY(hipSetDevice(c->devs[local].hip_id));
+  return cbx::stats_last_ms(c->devs[local].stats, pass_ms, total_ms);
+}
+
+int cbx_set_checkpoint_guard(cbx_context *c, int enable) {
+  TRY(check_ctx_q(c));
+  c->checkpoint_guard = enable != 0;
+  return CBX_OK;
+}
+
+// The checkpoint guard: CBX_ERR_STATE naming the first buffer (and its first
+// variable) that holds a non-finite value, among what the checkpoint stores.
+static int checkpoint_guard(cbx_context *c) {
+  TRY(wait_streams(c));
+  const size_t V = c->stats_vars.size();
+  std::vector<cbx_buffer_stats> totals, vars;
+  for (Device &d : c->devs) {
+    const size_t nb = d.replicas.size() + 1;
+    for (int kind : {CBX_BUF_DATA, CBX_BUF_LAST}) {
+      if (!base_has(c, kind)) continue;
+      TRY(device_stats(c, d, kind, kind, totals, &vars));
+      for (size_t b = 0; b < nb; ++b) {
+        if (totals[b].nonfinite == 0) continue;
+        size_t v = 0;
+        while (v + 1 < V && vars[v * nb + b].nonfinite == 0) ++v;
+        const cbx_context::StatsVar &sv = c->stats_vars[v];
+        const std::string who = b == 0 ? fmt("the base model of device %d", d.g) : fmt("replica %d", d.replicas[b - 1]);
+        return fail(CBX_ERR_STATE,
+                    "checkpoint refused: %s holds %llu non-finite values in its %s buffer, the first in variable %zu "
+                    "(op %d, order %d)",
+                    who.c_str(), totals[b].nonfinite, kind == CBX_BUF_DATA ? "data" : "last", v, sv.op, sv.order);
+      }
+    }
+  }
+  return CBX_OK;
+}
+
 // ---- checkpoint -----------------------------------------------------------
 static int batchnorm_checkpoint(cbx_context *c, const std::string &dir, bool store);
-static int wait_streams(cbx_context *c);  // cbx_wait without the peer-read poison check
 
 int cbx_checkpoint_model(cbx_context *c, const char *dir) {
   TraceRange trace("cbx_checkpoint_model");
   TRY(check_manager(c));
   if (!dir) return fail(CBX_ERR_INVALID, "null checkpoint directory");
+  if (c->checkpoint_guard) TRY(checkpoint_guard(c));  // before the version moves and the directory exists
   // executioncontext.c:2340-2350: dir/%06llu, a new version per call.
   std::string path = fmt("%s/%06llu", dir, ++c->version);
   if (mkdir(path.c_str(), 0777) < 0 && !(c->per_rank && errno == EEXIST))

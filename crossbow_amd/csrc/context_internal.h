@@ -37,6 +37,7 @@
 
 #include "../../include/crossbow_sma.h"
 #include "sma_internal.h"
+#include "stats_internal.h"
 
 namespace cbx::host {
 
@@ -387,6 +388,7 @@ struct Device {
   size_t bn_table_bytes = 0;
   float *bn_scratch = nullptr;         // packed statistics, all-reduced
   size_t bn_scratch_bytes = 0;
+  cbx::StatsScratch stats;             // cbx_model_stats: piece table, slab, results
   int num_cus = 256;
   // Arena: [base data][base gradient(ctrl+acc)][base diff(ctrl+D)][base last]
   //        then per replica [data][diff][last][gradient].
@@ -492,6 +494,14 @@ struct cbx_context {
   int64_t n4 = 0;      // padded float4 count
   bool has_last = false;
   unsigned long long version = 0;
+  bool checkpoint_guard = false;  // cbx_set_checkpoint_guard
+  // The model's variables in offset order as cbx_model_variable_info reports
+  // them (filled by cbx_set_model_manager): op -1 stands for the whole model.
+  struct StatsVar {
+    int op, order;
+    long long offset, elements;
+  };
+  std::vector<StatsVar> stats_vars;
   // BN operators whose running statistics travel with the checkpoint
   // (executioncontext.c:2352-2364): op id -> per-local-device buffers.
   struct BnStats {
@@ -834,6 +844,7 @@ inline void close_device(Device &d) {
     if (p) (void)hipHostFree(p);
   if (d.bn_table) (void)hipFree(d.bn_table);
   if (d.bn_scratch) (void)hipFree(d.bn_scratch);
+  cbx::stats_free(d.stats);
   if (d.host) (void)hipHostFree(d.host);
   if (d.synched) (void)hipEventDestroy(d.synched);
   for (int k = 0; k < EV_COUNT; ++k)

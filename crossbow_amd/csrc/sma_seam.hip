@@ -78,6 +78,7 @@ struct cbx_sma_plan {
     size_t bn_table_bytes = 0;
     float *bn_scratch = nullptr;
     size_t bn_scratch_bytes = 0;
+    cbx::StatsScratch stats;  // cbx_sma_plan_buffer_stats: piece table, slab, results
   };
   std::vector<Dev> devs;
   int64_t n = 0;
@@ -119,6 +120,7 @@ int cbx_sma_plan_free(cbx_sma_plan *p) {
     if (d.scratch) (void)hipFree(d.scratch);
     if (d.bn_table) (void)hipFree(d.bn_table);
     if (d.bn_scratch) (void)hipFree(d.bn_scratch);
+    cbx::stats_free(d.stats);
     for (hipEvent_t e : d.ev_a) (void)hipEventDestroy(e);
     for (hipEvent_t e : d.ev_r) (void)hipEventDestroy(e);
     if (d.comm_stream) (void)hipStreamDestroy(d.comm_stream);
@@ -501,6 +503,31 @@ int cbx_sma_plan_set_buckets(cbx_sma_plan *p, int buckets) {
   if (!p) return fail(CBX_ERR_INVALID, "null plan");
   if (buckets < 0 || buckets > 4096) return fail(CBX_ERR_INVALID, "plan buckets must be 0..4096, got %d", buckets);
   p->buckets = buckets;
+  return CBX_OK;
+}
+
+int cbx_sma_plan_buffer_stats(cbx_sma_plan *p, int k, void *stream, const float *ref, const float *const *bufs,
+                              int nbufs, const long long *var_elements, int nvars, cbx_buffer_stats *ref_out,
+                              cbx_buffer_stats *out, cbx_buffer_stats *ref_vars, cbx_buffer_stats *vars) {
+  TraceRange trace("cbx_sma_plan_buffer_stats");
+  if (!p) return fail(CBX_ERR_INVALID, "null plan");
+  if (k < 0 || k >= (int)p->devs.size()) return fail(CBX_ERR_INVALID, "plan device %d out of range", k);
+  if (!ref_out || (nbufs > 0 && !out) || nbufs < 0 || nbufs > cbx::kMaxReplicas || nvars < 0)
+    return fail(CBX_ERR_INVALID, "cbx_sma_plan_buffer_stats: bad buffer count or null result array");
+  auto &d = p->devs[k];
+  HIP_TRY(hipSetDevice(d.hip_id));
+  const size_t nb = (size_t)nbufs + 1, V = nvars > 0 ? (size_t)nvars : 1;
+  std::vector<cbx_buffer_stats> totals(nb), pv;
+  const bool want_vars = ref_vars || vars;
+  if (want_vars) pv.resize(V * nb);
+  TRY(cbx::stats_run(d.stats, static_cast<hipStream_t>(stream), ref, bufs, nbufs, var_elements, nvars, p->n,
+                     totals.data(), want_vars ? pv.data() : nullptr));
+  *ref_out = totals[0];
+  for (int i = 0; i < nbufs; ++i) out[i] = totals[1 + i];
+  for (size_t v = 0; v < V; ++v) {
+    if (ref_vars) ref_vars[v] = pv[v * nb];
+    for (int i = 0; vars && i < nbufs; ++i) vars[(size_t)i * V + v] = pv[v * nb + 1 + i];
+  }
   return CBX_OK;
 }
 

@@ -92,6 +92,32 @@ class SmaPlan:
             self._p, len(elements), _ints(elements), _ptrs(mean), _ptrs(variance), _ints(updated)),
             "cbx_sma_plan_average_batchnorm")
 
+    def buffer_stats(self, k: int, stream: int, ref: int, bufs: Sequence[int],
+                     var_elements: Optional[Sequence[int]] = None, per_variable: bool = False):
+        """``cbx_sma_plan_buffer_stats`` on the plan's device ``k``: the
+        statistics of ``ref`` and of each of ``bufs`` against it (device
+        pointers of ``elements`` floats).  Returns ``(ref, bufs)`` as numpy
+        structured arrays of shapes () and (len(bufs),); with ``per_variable``
+        also ``(ref_vars, buf_vars)`` of shapes (V,) and (len(bufs), V)."""
+        import numpy as np
+        fields = [("sum", "<f8"), ("sum_sq", "<f8"), ("dist_sq", "<f8"), ("nonfinite", "<u8"),
+                  ("max_abs", "<f4"), ("reserved", "<u4")]
+        dt = np.dtype(fields)
+        nv = len(var_elements) if var_elements else 0
+        V = max(1, nv)
+        ve = (ctypes.c_longlong * V)(*(var_elements or [0]))
+        r, o = np.zeros(1, dtype=dt), np.zeros(max(1, len(bufs)), dtype=dt)
+        rv, ov = np.zeros(V, dtype=dt), np.zeros((max(1, len(bufs)), V), dtype=dt)
+        bs = self.lib.cbx_sma_plan_buffer_stats.argtypes[8]
+
+        def p(a):
+            return ctypes.cast(a.ctypes.data, bs)
+        _raise(self.lib, self.lib.cbx_sma_plan_buffer_stats(
+            self._p, k, stream or None, ref, _ptrs(bufs), len(bufs), ve if nv else None, nv, p(r), p(o),
+            p(rv) if per_variable else None, p(ov) if per_variable else None), "cbx_sma_plan_buffer_stats")
+        o, ov = o[:len(bufs)], ov[:len(bufs)]
+        return (r[0], o, rv, ov) if per_variable else (r[0], o)
+
     def set_buckets(self, buckets: int) -> None:
         """G > 1: buckets of the all-reduce pipeline (0 = default 8, 1 = in order)."""
         _raise(self.lib, self.lib.cbx_sma_plan_set_buckets(self._p, buckets), "cbx_sma_plan_set_buckets")

@@ -190,6 +190,54 @@ class TheGPU:
     def delModel(self) -> int:
         return check(self._L.cbx_del_model(self._ctx))
 
+    # ---- model statistics (the reference checksums on the host, databuffer.c:141-162)
+    def modelVariables(self) -> list:
+        """The model's variables in offset order, as ``modelStats`` indexes
+        them: dicts of op, order, offset (elements) and elements."""
+        n = ctypes.c_int(0)
+        check(self._L.cbx_model_variable_count(self._ctx, ctypes.byref(n)))
+        out = []
+        for v in range(n.value):
+            op, order = ctypes.c_int(0), ctypes.c_int(0)
+            off, el = ctypes.c_longlong(0), ctypes.c_longlong(0)
+            check(self._L.cbx_model_variable_info(self._ctx, v, ctypes.byref(op), ctypes.byref(order),
+                                                  ctypes.byref(off), ctypes.byref(el)))
+            out.append({"op": op.value, "order": order.value, "offset": off.value, "elements": el.value})
+        return out
+
+    def modelStats(self, kind: int = _lib.BUF_DATA, per_variable: bool = False):
+        """``cbx_model_stats``: numpy structured arrays with the fields of
+        ``cbx_buffer_stats``.  Returns ``(base, replicas)``, shapes (local
+        devices,) and (replicas,); with ``per_variable`` also ``(base_vars,
+        replica_vars)``, shapes (local devices, V) and (replicas, V)."""
+        dt = np.dtype(_lib.BUFFER_STATS_FIELDS)
+        K = check(self._L.cbx_num_local_devices(self._ctx))
+        N = self.num_replicas()
+        base, reps = np.zeros(K, dtype=dt), np.zeros(N, dtype=dt)
+        bs = ctypes.POINTER(_lib.BufferStats)
+
+        def p(a):
+            return ctypes.cast(a.ctypes.data, bs)
+        if not per_variable:
+            check(self._L.cbx_model_stats(self._ctx, kind, p(base), p(reps), None, None))
+            return base, reps
+        V = len(self.modelVariables())
+        bv, rv = np.zeros((K, V), dtype=dt), np.zeros((N, V), dtype=dt)
+        check(self._L.cbx_model_stats(self._ctx, kind, p(base), p(reps), p(bv), p(rv)))
+        return base, reps, bv, rv
+
+    def model_stats_last_ms(self, local: int = 0):
+        """Device ms of the last ``modelStats`` on a local device: (the pass
+        over memory, the pass with its reductions)."""
+        a, b = ctypes.c_float(-1), ctypes.c_float(-1)
+        check(self._L.cbx_model_stats_last_ms(self._ctx, local, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+    def setCheckpointGuard(self, flag: bool) -> int:
+        """When on, ``checkpointModel`` refuses (CBX_ERR_STATE) a model that
+        holds a non-finite value, before it numbers or creates the folder."""
+        return check(self._L.cbx_set_checkpoint_guard(self._ctx, 1 if flag else 0))
+
     # ---- batch-norm running statistics (cudnnbatchnormparams.c:102-222) ------
     def register_batchnorm_stats(self, op: int, elements: int, mean_ptrs: Sequence[int],
                                  var_ptrs: Sequence[int]) -> None:

@@ -185,6 +185,56 @@ int cbx_register_batchnorm_stats (cbx_context *ctx, int op, int elements,
 int cbx_add_model (cbx_context *ctx);
 int cbx_del_model (cbx_context *ctx);
 
+/* ---- model statistics and replica divergence --------------------------- */
+/* The reference can only checksum a buffer on the host, with a loop on every
+ * store and load (clib-multigpu/databuffer.c:141-162, called at :218 and
+ * :255, behind its COMPUTE_CHECKSUM debug switch).  Here one pass over HBM
+ * reduces the base model and every local replica on the device, per model
+ * variable and per buffer (crossbow_amd/csrc/stats_kernels.hip).  Sums are
+ * accumulated in fp64 from the first add, in an order that depends on the
+ * variable list alone: two calls on the same data return the same bits.    */
+typedef struct cbx_buffer_stats {
+  double sum;                   /* sum of x over finite x                        */
+  double sum_sq;                /* sum of x*x over finite x                      */
+  double dist_sq;               /* sum of (x - ref)^2 where x and ref are both finite;
+                                   0 for the reference buffer itself            */
+  unsigned long long nonfinite; /* NaN or +-inf among x                          */
+  float  max_abs;               /* max |x| over finite x, 0 if there is none     */
+  unsigned int reserved;        /* 0                                             */
+} cbx_buffer_stats;             /* 40 bytes, no implicit padding                 */
+/* The registered variables in ascending offset order; index v below is the
+ * position in that order.  A model registered as raw bytes (no variables),
+ * or one whose variables do not tile its elements (a capacity above its
+ * shape's bytes), reports one variable: op -1, order 0, every element.
+ * CBX_ERR_STATE before cbx_set_model_manager.                             */
+int cbx_model_variable_count (cbx_context *ctx, int *count);
+int cbx_model_variable_info (cbx_context *ctx, int v, int *op, int *order,
+		long long *offset_elements, long long *elements);
+/* kind CBX_BUF_DATA measures every w against z, CBX_BUF_DIFF every s against
+ * z (anything else: CBX_ERR_INVALID).  base[k]: z of local device k (dist_sq
+ * 0); replicas[id] for every id in 0..cbx_num_replicas, zeroed for a replica
+ * of another process; base_vars[k * V + v] and replica_vars[id * V + v] the
+ * same per variable (V = cbx_model_variable_count; either may be NULL).
+ * Blocking: drains the library's streams as the checkpoint does (no poison
+ * check: looking at a damaged model is its job, so a broken peer-read step
+ * does not refuse it), launches on each local device's sync stream and
+ * returns with the numbers on the host.  It only reads model buffers, so a
+ * cross-step pipeline stays valid.  Every local replica is covered, locked
+ * or not: a caller who wants consistent numbers calls it between
+ * cbx_lock_any and cbx_unlock_any.                                        */
+int cbx_model_stats (cbx_context *ctx, int kind, cbx_buffer_stats *base, cbx_buffer_stats *replicas,
+		cbx_buffer_stats *base_vars, cbx_buffer_stats *replica_vars);
+/* Device milliseconds of the last cbx_model_stats on local device `local`,
+ * from the dispatches' own timestamps: the pass over memory alone, and the
+ * pass with its two reductions; -1 before the first call.                 */
+int cbx_model_stats_last_ms (cbx_context *ctx, int local, float *pass_ms, float *total_ms);
+/* Checkpoint guard, default off.  When on, cbx_checkpoint_model first runs
+ * the reduction over z and every local w (and over the base and replica
+ * `last` when momentum > 0) and, if any holds a non-finite value, returns
+ * CBX_ERR_STATE naming the first such buffer and variable; it then creates
+ * no directory and does not advance the version numbering.                */
+int cbx_set_checkpoint_guard (cbx_context *ctx, int enable);
+
 /* ---- batch-norm running statistics ----------------------------------- */
 /* crossbowCudnnBatchNormParamsSynchroniseEstimatedMeanAndVariable
  * (cudnn/cudnnbatchnormparams.c:157-222; its caller is commented out at
@@ -610,6 +660,19 @@ int cbx_sma_plan_set_buckets (cbx_sma_plan *plan, int buckets);
 int cbx_sma_plan_step (cbx_sma_plan *plan, void *const *streams, float *const *z, float *const *last,
                        int nreplicas, const int *replica_device, float *const *w, const float *const *s,
                        const int *locked, const int *copy, float alpha, float momentum, int first);
+/* The statistics reduction of cbx_model_stats over caller-owned buffers of
+ * exactly the plan's `elements` floats on the plan's device k (where a
+ * Crossbow build would checksum, databuffer.c:141-162): `ref` against
+ * bufs[0..nbufs) (0..64 buffers).  var_elements[0..nvars) are the variables'
+ * float counts in offset order and must sum to `elements`; nvars = 0 means
+ * one variable.  ref_out: 1 record; out: nbufs; ref_vars: nvars (or 1);
+ * vars: [i * nvars + v]; the last two may be NULL.  The scratch is the
+ * plan's (one call at a time per plan device).  Enqueues on `stream`
+ * (hipStream_t of that device) and blocks on it before returning.          */
+int cbx_sma_plan_buffer_stats (cbx_sma_plan *plan, int k, void *stream, const float *ref,
+                               const float *const *bufs, int nbufs, const long long *var_elements, int nvars,
+                               cbx_buffer_stats *ref_out, cbx_buffer_stats *out, cbx_buffer_stats *ref_vars,
+                               cbx_buffer_stats *vars);
 /* The replica's optimiser step of one task (sma.cu:3-100) in one pass over
  * its buffers, on `stream` (hipStream_t, the task stream; the current HIP
  * device must be the buffers'): w = model->data, g = model->gradient

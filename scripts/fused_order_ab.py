@@ -85,7 +85,7 @@ def build():
             src = src.replace(old, new, 1)
         open(k, "w").write(src)
         objs = []
-        for f in ("context.hip", "sync_steps.hip", "sma_kernels.hip", "sma_seam.hip"):
+        for f in ("context.hip", "sync_steps.hip", "sma_kernels.hip", "sma_seam.hip", "stats_kernels.hip"):
             o = os.path.join(d, f.replace(".hip", ".o"))
             subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall",
                             f"-cuid=crossbow_{f[:-4]}", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
