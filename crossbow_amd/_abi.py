@@ -29,7 +29,7 @@ ERROR_NAMES = {
 BUF_DATA, BUF_GRADIENT, BUF_DIFF, BUF_LAST = 0, 1, 2, 3
 T_KERNEL, T_ALLREDUCE, T_APPLY, T_STEP, T_H2D, T_D2H, T_COUNT = range(7)
 SYNC_BSP, SYNC_SSP, SYNC_ASP = 0, 1, 2
-UPDATE_DEFAULT, UPDATE_WORKER, UPDATE_SYNCHRONOUSEAMSGD, UPDATE_SMA = 0, 1, 3, 7
+UPDATE_DEFAULT, UPDATE_WORKER, UPDATE_SYNCHRONOUSEAMSGD, UPDATE_POLYAK_RUPPERT, UPDATE_SMA = 0, 1, 3, 6, 7
 ALLREDUCE_RCCL, ALLREDUCE_PEER, ALLREDUCE_RSAG = 0, 1, 2
 PEER_BLOB_BYTES = 256  # CBX_PEER_BLOB_BYTES
 STAGING_ZEROCOPY, STAGING_DMA = 0, 1
@@ -82,6 +82,7 @@ SIGNATURES = {
     "cbx_set_model_variable_learning_rate_multiplier": (_I, [_P, _I, _I, _F]),
     "cbx_set_model_work_per_clock": (_I, [_P, _I]),
     "cbx_set_update_model_type": (_I, [_P, _I]),
+    "cbx_set_elastic_average": (_I, [_P, _I]),
     "cbx_set_learning_rate_decay_policy_fixed": (_I, [_P, _F]),
     "cbx_set_learning_rate_decay_policy_inv": (_I, [_P, _F, _D, _D]),
     "cbx_set_learning_rate_decay_policy_step": (_I, [_P, _F, _D, _I]),
@@ -151,6 +152,7 @@ SIGNATURES = {
     "cbx_set_aux_kernel_config": (_I, [_P, _I, _I, _I]),
     "cbx_set_barrier_kernel_config": (_I, [_P, _I, _I, _I]),
     "cbx_set_apply_kernel_config": (_I, [_P, _I, _I, _I]),
+    "cbx_set_averaging_kernel_config": (_I, [_P, _I, _I, _I]),
     "cbx_set_pipeline_mode": (_I, [_P, _I]),
     "cbx_set_cross_wait_stride": (_I, [_P, _I]),
     "cbx_set_allreduce_group": (_I, [_P, _I]),

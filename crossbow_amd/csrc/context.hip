@@ -539,23 +539,31 @@ static int synchronise_impl(cbx_context *c, int first, int clock, int autotune, 
   // One process per GPU: no collective step of any form once a rank is broken.
   if (c->G > 1) TRY(peer_guard(c, staged ? "cbx_synchronise_staged" : "cbx_synchronise"));
   // executioncontext.c:2287-2315: SYNCHRONOUSEAMSGD (3) routes to SMA because
-  // ELASTIC_AVERAGE is #undef'd; SMA is 7.  The other update models are not
-  // this library's path.
+  // ELASTIC_AVERAGE is #undef'd in the reference's default build, and to
+  // elastic averaging where it is defined (cbx_set_elastic_average); SMA is 7.
   // WORKER (1) is synchronous SGD (executioncontext.c:2277-2279), which shares
-  // the base-model buffers and the all-reduce.
+  // the base-model buffers and the all-reduce; POLYAK_RUPPERT (6) is :2307-2309.
+  // The other update models are not this library's path.
   const int type = c->model.type;
-  if (staged || (type != CBX_UPDATE_SMA && type != CBX_UPDATE_SYNCHRONOUSEAMSGD)) {
+  const bool elastic = type == CBX_UPDATE_SYNCHRONOUSEAMSGD && c->elastic_average;
+  const bool sma = (type == CBX_UPDATE_SMA || type == CBX_UPDATE_SYNCHRONOUSEAMSGD) && !elastic;
+  if (staged || !sma) {
     c->foreign_ops.fetch_add(1, std::memory_order_relaxed);
     for (Device &d : c->devs) d.cross_valid = false;
   }
-  if (type == CBX_UPDATE_WORKER || type == CBX_UPDATE_DEFAULT) {
-    if (staged) TRY(cbx_stage_in(c));
-    TRY(type == CBX_UPDATE_WORKER ? ssgd_step(c, first) : default_step(c, first));
-    if (staged) TRY(cbx_stage_out(c));
-  } else if (type == CBX_UPDATE_SMA || type == CBX_UPDATE_SYNCHRONOUSEAMSGD) {
+  if (sma) {
     TRY(staged ? sma_step_staged(c, first, staged) : sma_step(c, first));
+  } else if (type == CBX_UPDATE_WORKER || type == CBX_UPDATE_DEFAULT || elastic || type == CBX_UPDATE_POLYAK_RUPPERT) {
+    if (type == CBX_UPDATE_POLYAK_RUPPERT && clock < 0)  // before anything is staged in
+      return fail(CBX_ERR_INVALID, "Polyak-Ruppert averaging needs a clock >= 0, got %d", clock);
+    if (staged) TRY(cbx_stage_in(c));
+    if (type == CBX_UPDATE_WORKER) TRY(ssgd_step(c, first));
+    else if (type == CBX_UPDATE_DEFAULT) TRY(default_step(c, first));
+    else TRY(averaging_step(c, first, clock, type == CBX_UPDATE_POLYAK_RUPPERT));
+    if (staged) TRY(cbx_stage_out(c));
   } else {
-    return fail(CBX_ERR_UNSUPPORTED, "update model %d is not on this library's path (SMA, SYNCHRONOUSEAMSGD, WORKER, DEFAULT)", type);
+    return fail(CBX_ERR_UNSUPPORTED,
+                "update model %d is not on this library's path (SMA, SYNCHRONOUSEAMSGD, POLYAK_RUPPERT, WORKER, DEFAULT)", type);
   }
   if (autotune < 0) TRY(cbx_del_model(c));
   if (autotune > 0) TRY(cbx_add_model(c));
@@ -1739,6 +1747,7 @@ int cbx_set_kernel_config(cbx_context *c, int block, int blocks_per_cu, int poli
   c->cfg.blocks_per_cu = blocks_per_cu;
   c->cfg.policy = policy;
   c->apply_cfg.policy = policy;  // load/store policy is shared; kernel B keeps its own geometry
+  c->avg_cfg.policy = policy;    // and so do the averaging kernels
   c->cfg.unroll = unroll;
   return CBX_OK;
 }
@@ -1788,6 +1797,19 @@ int cbx_set_apply_kernel_config(cbx_context *c, int block, int unroll, int waves
   c->apply_cfg.block = block;
   c->apply_cfg.unroll = unroll;
   c->apply_cfg.waves_per_cu = waves_per_cu;
+  return CBX_OK;
+}
+
+int cbx_set_averaging_kernel_config(cbx_context *c, int block, int unroll, int waves_per_cu) {
+  TRY(check_ctx(c));
+  if (block < 64 || block > 256 || block % 64 != 0) return fail(CBX_ERR_INVALID, "block must be 64..256, multiple of 64");
+  if (unroll != 1 && unroll != 2 && unroll != 4) return fail(CBX_ERR_INVALID, "unroll must be 1, 2 or 4");
+  if ((int64_t)block * unroll > cbx::kPadFloat4 || cbx::kPadFloat4 % ((int64_t)block * unroll) != 0)
+    return fail(CBX_ERR_INVALID, "block*unroll must divide %lld", (long long)cbx::kPadFloat4);
+  if (waves_per_cu < -1 || waves_per_cu > 32) return fail(CBX_ERR_INVALID, "waves per CU must be -1 (auto) or 0..32");
+  c->avg_cfg.block = block;
+  c->avg_cfg.unroll = unroll;
+  c->avg_cfg.waves_per_cu = waves_per_cu;
   return CBX_OK;
 }
 
@@ -1864,6 +1886,13 @@ int cbx_set_bucket_elements(cbx_context *c, long long bucket_elements) {
 int cbx_set_force_split(cbx_context *c, int force) {
   TRY(check_ctx(c));
   c->force_split = force != 0;
+  return CBX_OK;
+}
+
+int cbx_set_elastic_average(cbx_context *c, int enable) {
+  TRY(check_ctx(c));
+  if (enable != 0 && enable != 1) return fail(CBX_ERR_INVALID, "elastic average must be 0 or 1, got %d", enable);
+  c->elastic_average = enable == 1;
   return CBX_OK;
 }
 

@@ -516,10 +516,13 @@ struct cbx_context {
   // Write-heavy barrier kernels of DEFAULT and S-SGD (scripts/barrier_sweep.py).
   cbx::LaunchConfig broadcast_cfg = cbx::broadcast_launch_config();
   cbx::LaunchConfig ssgd_apply_cfg = cbx::ssgd_apply_launch_config();
+  // Fused and accumulate-only kernels of elastic averaging and Polyak-Ruppert (scripts/bench_averaging.py --sweep).
+  cbx::LaunchConfig avg_cfg = cbx::averaging_launch_config();
   // Kernel B of the split SMA path (scripts/apply_sweep.py).
   cbx::LaunchConfig apply_cfg = cbx::sma_apply_launch_config();
   int64_t bucket_elems = 0;
   bool force_split = false;
+  bool elastic_average = false;  // cbx_set_elastic_average: update model 3 runs EA-SGD, not SMA
   bool last_step_split = false;
   int pipeline_mode = 0;  // 0 bucketed within a step, 1 across steps (G > 1 split path)
   int cross_wait_stride = 1;  // mode 1: buckets per cross-step wait
@@ -1053,6 +1056,10 @@ int sma_step(cbx_context *c, int first);
 int sma_step_staged(cbx_context *c, int first, int buckets);
 // Synchronous SGD, update model WORKER (synch/synchronoussgd.c:13-106).
 int ssgd_step(cbx_context *c, int first);
+// Elastic averaging (synch/synchronouseamsgd.c:5-305; update model 3 with
+// cbx_set_elastic_average) or, with `polyak`, Polyak-Ruppert averaging
+// (synch/polyakruppert.c:5-317; update model 6), which divides by `clock` + 1.
+int averaging_step(cbx_context *c, int first, int clock, bool polyak);
 // RCCL communicators on first use (one-rank, or a clique that repeats a device).
 int ensure_comms(cbx_context *c);
 // The step event of every device (cbx_step_event), after a step's last dispatch.

@@ -72,6 +72,10 @@ struct LaunchConfig {
 };
 
 constexpr int kStreamsPerCU = 56;
+// The averaging kernels hold one float4 per stream and lane where the SMA
+// step holds two, and run fastest with more streams in flight per CU: 4 waves
+// of 18 (elastic averaging) or 19 (Polyak-Ruppert) at R = 8.
+constexpr int kAveragingStreamsPerCU = 76;
 
 // The optimiser-step and S-SGD kernels: one-wave workgroups, one float4 per
 // lane, auto occupancy (scripts/aux_sweep.py).
@@ -113,6 +117,19 @@ inline LaunchConfig staged_launch_config() {
   c.unroll = 2;
   c.blocks_per_cu = 4;
   c.waves_per_cu = 0;
+  return c;
+}
+// The fused and accumulate-only kernels of the elastic-averaging and
+// Polyak-Ruppert barriers (averaging_kernels.hip): one-wave blocks, one float4
+// per lane, auto occupancy from kAveragingStreamsPerCU
+// (scripts/bench_averaging.py --sweep, profiles/averaging/sweep.jsonl:
+// ResNet-50, R = 8); cbx_set_averaging_kernel_config overrides it.  Their
+// apply kernel is shaped like SMA's kernel B (sma_apply_launch_config).
+inline LaunchConfig averaging_launch_config() {
+  LaunchConfig c;
+  c.block = 64;
+  c.unroll = 1;
+  c.waves_per_cu = -1;
   return c;
 }
 inline LaunchConfig ssgd_apply_launch_config() {
@@ -314,6 +331,38 @@ hipError_t launch_ssgd_accumulate(const SsgdArgs &a, const LaunchConfig &cfg, hi
 // Barrier (synchronoussgd.c:13-106, common.c:198-220): D *= 1/wpc; momentum;
 // z += D; acc = 0; every locked replica := z.
 hipError_t launch_ssgd_apply(const SsgdArgs &a, const LaunchConfig &cfg, hipStream_t stream, Timing t = {});
+// The elastic-averaging barrier (update model SYNCHRONOUSEAMSGD with
+// cbx_set_elastic_average, synch/synchronouseamsgd.c) and the Polyak-Ruppert
+// barrier (update model POLYAK_RUPPERT, synch/polyakruppert.c): one kernel
+// family, averaging_kernels.hip.
+enum AvgModel {
+  kElasticW = 0,  // elastic averaging, d from the replica's data (one device, synchronouseamsgd.c:42-90)
+  kElasticS = 1,  // elastic averaging, d from the replica's snapshot (G > 1, :141-273)
+  kPolyak = 2,    // Polyak-Ruppert (polyakruppert.c:42-137)
+};
+struct AvgArgs {
+  const v4f *s[kMaxReplicas];  // replica snapshots (kElasticS only)
+  v4f *w[kMaxReplicas];        // replica parameters
+  v4f *z;                      // base model
+  v4f *last;                   // kPolyak: base->last, left holding acc - z (may be null)
+  v4f *acc;                    // accumulate-only phase: its output
+  const v4f *D;                // apply phase: the all-reduced acc
+  int64_t n4;                  // float4s in the launch's range (multiple of kPadFloat4)
+  uint64_t copy_mask;          // kPolyak: bit r set = a.w[r] becomes z (its copy flag is raised)
+  float alpha;                 // conf->alpha
+  float scale;                 // kPolyak: 1 / replicas (polyakruppert.c:15)
+  float running;               // kPolyak: 1 / (clock + 1) (:16)
+  int nrep;                    // locked replicas on this device, id order
+};
+// One device (and not forced to split): the whole step in one pass.
+hipError_t launch_averaging_fused(AvgModel m, const AvgArgs &a, const LaunchConfig &cfg, hipStream_t stream,
+                                  Timing t = {});
+// Phase A: the replica loop only, acc written out for the all-reduce.
+hipError_t launch_averaging_accumulate(AvgModel m, const AvgArgs &a, const LaunchConfig &cfg, hipStream_t stream,
+                                       Timing t = {});
+// Phase B: the base-model update from the all-reduced D (and kPolyak's copies).
+hipError_t launch_averaging_apply(AvgModel m, const AvgArgs &a, const LaunchConfig &cfg, hipStream_t stream,
+                                  Timing t = {});
 // Batch-norm running-statistics averaging (cudnn/cudnnbatchnormparams.c:157-222):
 // every (layer, mean|variance) buffer of a device is one segment of a packed
 // scratch buffer that a single all-reduce sums across devices.

@@ -1753,6 +1753,154 @@ int ssgd_step(cbx_context *c, int first) {
 }
 
 // ---------------------------------------------------------------------------
+// Elastic averaging (synch/synchronouseamsgd.c:5-101 on one device, :106-305
+// on several) and Polyak-Ruppert averaging (synch/polyakruppert.c:5-138,
+// :140-317).  One fused kernel at G = 1.  At G > 1 (or forced) each device
+// accumulates its own replicas (kernel A), acc is all-reduced into D, and
+// every device applies D to its z (kernel B): the reference chains every
+// replica into the default device's acc over peer copies and broadcasts z,
+// so the two differ in summation order only, and z is the same bits on every
+// device.  Buckets as in ssgd_step; with more than one, the
+// all-reduce of bucket k runs on comm_stream beside kernel A of bucket k + 1:
+//   stream      : A(0) A(1) [wait red(0)] B(0) A(2) [wait red(1)] B(1) ...
+//   comm_stream : [wait acc(0)] AR(0) [wait acc(1)] AR(1) ...
+// The next step's A(0) follows this step's last B on the same stream, and
+// its AR(k) waits for its A(k): no buffer is rewritten while still in use.
+// ---------------------------------------------------------------------------
+int averaging_step(cbx_context *c, int first, int clock, bool polyak) {
+  // polyakruppert.c:16 divides by clock + 1: the caller has refused clock < 0
+  const bool split = c->G > 1 || c->force_split;
+  if (split) TRY(ensure_comms(c));
+  // synchronouseamsgd.c:55 reads the replica's data on one device, :184 its snapshot on several
+  const cbx::AvgModel model = polyak ? cbx::kPolyak : (c->G > 1 ? cbx::kElasticS : cbx::kElasticW);
+  std::vector<cbx::AvgArgs> args(c->devs.size());
+  for (size_t k = 0; k < c->devs.size(); ++k) {
+    Device &d = c->devs[k];
+    cbx::AvgArgs &a = args[k];
+    std::memset(&a, 0, sizeof(a));
+    int r = 0;
+    for (int id : d.replicas) {  // increasing id order
+      if (id < first || !c->locked[id]) continue;
+      if (r >= cbx::kMaxReplicas)
+        return fail(CBX_ERR_UNSUPPORTED, "more than %d locked replicas on one device", cbx::kMaxReplicas);
+      Replica &rep = *c->replicas[id];
+      a.s[r] = reinterpret_cast<const cbx::v4f *>(replica_dev(d, rep, CBX_BUF_DIFF));
+      a.w[r] = reinterpret_cast<cbx::v4f *>(replica_dev(d, rep, CBX_BUF_DATA));
+      if (polyak && rep.conf.copy) a.copy_mask |= 1ull << r;  // polyakruppert.c:126
+      ++r;
+    }
+    a.nrep = r;
+    a.z = reinterpret_cast<cbx::v4f *>(base_dev(c, d, CBX_BUF_DATA));
+    a.last = polyak && c->has_last ? reinterpret_cast<cbx::v4f *>(base_dev(c, d, CBX_BUF_LAST)) : nullptr;
+    a.acc = reinterpret_cast<cbx::v4f *>(base_dev(c, d, CBX_BUF_GRADIENT));
+    a.D = reinterpret_cast<const cbx::v4f *>(base_dev(c, d, CBX_BUF_DIFF));
+    a.n4 = c->n4;
+    a.alpha = c->model.conf.alpha;
+    a.scale = (float)(1.0 / (double)(float)c->size.load());  // polyakruppert.c:15
+    a.running = (float)(1.0 / (double)(float)(clock + 1));   // :16
+  }
+  auto range = [](const cbx::AvgArgs &a, int64_t start4, int64_t len4) {
+    cbx::AvgArgs b = a;
+    for (int r = 0; r < a.nrep; ++r) {
+      b.s[r] = a.s[r] + start4;
+      b.w[r] = a.w[r] + start4;
+    }
+    b.z = a.z + start4;
+    if (a.last) b.last = a.last + start4;
+    b.acc = a.acc + start4;
+    b.D = a.D + start4;
+    b.n4 = len4;
+    return b;
+  };
+  if (!split) {
+    Device &d = c->devs[0];
+    HIP_TRY(hipSetDevice(d.hip_id));
+    cbx::LaunchConfig cfg = c->avg_cfg;
+    cfg.num_cus = d.num_cus;
+    HIP_TRY(cbx::launch_averaging_fused(model, args[0], cfg, d.stream,
+                                        {step_start_event(c, d, 0), step_stop_event(c, d, EV_A)}));
+    ring_advance(c, d, 0);
+  } else {
+    int64_t b4 = c->n4;
+    const int64_t pad = cbx::kPadFloat4;
+    if (c->bucket_elems > 0) b4 = ((c->bucket_elems / 4 + pad - 1) / pad) * pad;
+    else if (c->G > 1) b4 = ((c->n4 / kDefaultBuckets + pad - 1) / pad) * pad;
+    if (b4 <= 0 || b4 > c->n4) b4 = c->n4;
+    const int64_t nb = (c->n4 + b4 - 1) / b4;
+    const bool pipelined = nb > 1;
+    for (Device &d : c->devs) {
+      HIP_TRY(hipSetDevice(d.hip_id));
+      if (pipelined) TRY(mark(c, d, EV_START));
+      while (pipelined && (int64_t)d.bucket_red.size() < nb) {
+        hipEvent_t ea, er, eb;
+        HIP_TRY(hipEventCreate(&ea));
+        HIP_TRY(hipEventCreateWithFlags(&er, hipEventDisableTiming));
+        HIP_TRY(hipEventCreate(&eb));
+        d.bucket_acc.push_back(ea);
+        d.bucket_red.push_back(er);
+        d.bucket_b.push_back(eb);
+      }
+    }
+    // Kernel B of bucket b on every device, once its all-reduce has landed.
+    auto apply = [&](int64_t b) -> int {
+      const int64_t start = b * b4, len = std::min(b4, c->n4 - start);
+      for (size_t k = 0; k < c->devs.size(); ++k) {
+        Device &d = c->devs[k];
+        HIP_TRY(hipSetDevice(d.hip_id));
+        if (pipelined) HIP_TRY(hipStreamWaitEvent(d.stream, d.bucket_red[b], 0));
+        cbx::LaunchConfig cfg = c->apply_cfg;
+        cfg.num_cus = d.num_cus;
+        cbx::Timing t;
+        if (b == nb - 1) t.stop = step_stop_event(c, d, EV_B);
+        HIP_TRY(cbx::launch_averaging_apply(model, range(args[k], start, len), cfg, d.stream, t));
+        if (b == nb - 1) ring_advance(c, d, pipelined ? 2 : 1);
+      }
+      return CBX_OK;
+    };
+    for (int64_t b = 0; b < nb; ++b) {
+      const int64_t start = b * b4, len = std::min(b4, c->n4 - start);
+      for (size_t k = 0; k < c->devs.size(); ++k) {
+        Device &d = c->devs[k];
+        HIP_TRY(hipSetDevice(d.hip_id));
+        cbx::LaunchConfig cfg = c->avg_cfg;
+        cfg.num_cus = d.num_cus;
+        cbx::Timing t;
+        if (!pipelined) t = {ring_event(c, d, EV_START), ring_event(c, d, EV_A)};
+        HIP_TRY(cbx::launch_averaging_accumulate(model, range(args[k], start, len), cfg, d.stream, t));
+        if (pipelined) {
+          HIP_TRY(hipEventRecord(d.bucket_acc[b], d.stream));
+          HIP_TRY(hipStreamWaitEvent(d.comm_stream, d.bucket_acc[b], 0));
+        }
+      }
+      NCCL_TRY(ncclGroupStart());
+      for (Device &d : c->devs) {
+        HIP_TRY(hipSetDevice(d.hip_id));
+        NCCL_TRY(ncclAllReduce(base_dev(c, d, CBX_BUF_GRADIENT) + start * 4, base_dev(c, d, CBX_BUF_DIFF) + start * 4,
+                               (size_t)len * 4, ncclFloat, ncclSum, d.comm, pipelined ? d.comm_stream : d.stream));
+      }
+      NCCL_TRY(ncclGroupEnd());
+      for (Device &d : c->devs) {
+        HIP_TRY(hipSetDevice(d.hip_id));
+        if (pipelined) HIP_TRY(hipEventRecord(d.bucket_red[b], d.comm_stream));
+        else TRY(mark(c, d, EV_AR));
+      }
+      if (b > 0) TRY(apply(b - 1));
+    }
+    TRY(apply(nb - 1));
+  }
+  for (Device &d : c->devs) d.cross_valid = false;
+  c->last_step_split = split;
+  TRY(finish_step(c));
+  if (polyak)
+    for (Device &d : c->devs)
+      for (int id : d.replicas) {
+        if (id < first || !c->locked[id]) continue;
+        c->replicas[id]->conf.copy = 0;  // polyakruppert.c:131 (only a raised flag changes)
+      }
+  return CBX_OK;
+}
+
+// ---------------------------------------------------------------------------
 // Stream-order check (cbx_set_order_check / cbx_check_order).  From the
 // timestamps a split step recorded, per bucket k on every device:
 //   the collective of k started after kernel A(k) ended;

@@ -113,6 +113,11 @@ class TheGPU:
     def setUpdateModelType(self, type: int) -> int:
         return check(self._L.cbx_set_update_model_type(self._ctx, type))
 
+    def setElasticAverage(self, enable: bool) -> int:
+        """The reference's compile-time ELASTIC_AVERAGE as a switch: update model
+        SYNCHRONOUSEAMSGD (3) runs elastic averaging instead of SMA."""
+        return check(self._L.cbx_set_elastic_average(self._ctx, 1 if enable else 0))
+
     # ---- solver (SolverConf.GPURegister, SolverConf.java:355-409) ----------
     def setLearningRateDecayPolicyFixed(self, rate: float) -> int:
         return check(self._L.cbx_set_learning_rate_decay_policy_fixed(self._ctx, rate))
@@ -447,6 +452,9 @@ class TheGPU:
     def set_apply_kernel_config(self, block: int, unroll: int, waves_per_cu: int) -> None:
         """Launch geometry of kernel B (Phase C) of the split SMA path."""
         check(self._L.cbx_set_apply_kernel_config(self._ctx, block, unroll, waves_per_cu))
+
+    def set_averaging_kernel_config(self, block: int = 64, unroll: int = 1, waves_per_cu: int = -1) -> None:
+        check(self._L.cbx_set_averaging_kernel_config(self._ctx, block, unroll, waves_per_cu))
 
     def set_pipeline_mode(self, mode: int) -> None:
         """0: buckets overlap within a step; 1: also across steps."""

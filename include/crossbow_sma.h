@@ -39,7 +39,8 @@ extern "C" {
 /* Update model ids, uk/ac/imperial/lsds/crossbow/types/UpdateModel.java:5 */
 #define CBX_UPDATE_DEFAULT           0   /* single GPU: synch/default.c, optimisers/default.cu */
 #define CBX_UPDATE_WORKER            1   /* synchronous SGD: synch/synchronoussgd.c */
-#define CBX_UPDATE_SYNCHRONOUSEAMSGD 3   /* routed to SMA: clib-multigpu/utils.h:56-57 */
+#define CBX_UPDATE_SYNCHRONOUSEAMSGD 3   /* SMA (clib-multigpu/utils.h:56-57), or elastic averaging: cbx_set_elastic_average */
+#define CBX_UPDATE_POLYAK_RUPPERT    6   /* synch/polyakruppert.c */
 #define CBX_UPDATE_SMA               7
 
 /* Synchronisation models, types/SynchronisationModel.java:5 */
@@ -87,8 +88,18 @@ int cbx_set_model_variable_buffer (cbx_context *ctx, int id, int order, const vo
 int cbx_set_model_variable_learning_rate_multiplier (cbx_context *ctx, int id, int order, float multiplier);
 /* TheGPU.setModelWorkPerClock(I)           GPU.c:721-730  */
 int cbx_set_model_work_per_clock (cbx_context *ctx, int wpc);
-/* TheGPU.setUpdateModelType(I)             GPU.c:732-741; 3 and 7 accepted */
+/* TheGPU.setUpdateModelType(I)             GPU.c:732-741.  0..7 are stored;
+ * cbx_synchronise runs 0, 1, 3, 6 and 7 (see there).                      */
 int cbx_set_update_model_type (cbx_context *ctx, int type);
+/* The reference's compile-time ELASTIC_AVERAGE (executioncontext.c:2287-2295)
+ * as a run-time switch.  0 (the default, the reference's default build):
+ * update model SYNCHRONOUSEAMSGD (3) runs SMA, exactly as SMA (7) does.
+ * 1: it runs the elastic-averaging barrier
+ * (crossbowSynchronisationSynchronousElasticAveragingSGD,
+ * synch/synchronouseamsgd.c:5-305).  SMA (7) is unaffected either way.
+ * May be set before or after cbx_set_model_manager; any other value is
+ * CBX_ERR_INVALID.                                                        */
+int cbx_set_elastic_average (cbx_context *ctx, int enable);
 
 /* ---- solver (SolverConf.GPURegister, SolverConf.java:355-409) --------- */
 /* TheGPU.setLearningRateDecayPolicy*  GPU.c:743-821 */
@@ -135,7 +146,24 @@ int cbx_merge (cbx_context *ctx, int pull, int *first);
  * synchronous-SGD barrier (synch/synchronoussgd.c:13-106, needs the work
  * per clock); DEFAULT (0) copies the base model to every locked replica
  * (synch/default.c:5-43; one GPU only, as in the reference: more devices
- * give CBX_ERR_UNSUPPORTED); any other is CBX_ERR_UNSUPPORTED.          */
+ * give CBX_ERR_UNSUPPORTED); any other is CBX_ERR_UNSUPPORTED.
+ * With cbx_set_elastic_average on, SYNCHRONOUSEAMSGD (3) runs elastic
+ * averaging instead (synch/synchronouseamsgd.c): every locked replica moves
+ * towards z by alpha * (w_i - z) and z by the sum of those moves; no
+ * momentum, the copy flags are neither read nor cleared.  On one device the
+ * difference is taken from the replica's data, on several from its snapshot
+ * (as the reference does), each device sums its own replicas and the sums
+ * are all-reduced, so z differs from the reference's single chain in
+ * summation order only.
+ * POLYAK_RUPPERT (6) runs synch/polyakruppert.c: acc = sum of w_i / p over
+ * the locked replicas (p = cbx_num_replicas, all of them), all-reduced;
+ * w_i moves towards z as above unless alpha is 0; then
+ * z += (acc - z) / (clock + 1), so over clocks 0, 1, ... z is the running
+ * average of the replica mean.  The base `last` buffer, where it exists,
+ * is left holding acc - z; only replicas whose copy flag is raised become
+ * z, and only their flag is cleared.  clock < 0 is CBX_ERR_INVALID.
+ * Both use the in-order bucketed all-reduce (cbx_set_bucket_elements) at
+ * G > 1, whatever cbx_set_allreduce_algorithm says.                       */
 int cbx_synchronise (cbx_context *ctx, int first, int clock, int autotune, int push);
 /* The same step for a model manager whose buffers live in host memory
  * (north_star: "starts and ends in host memory", databuffer.c:95-122):
@@ -146,7 +174,8 @@ int cbx_synchronise (cbx_context *ctx, int first, int clock, int autotune, int p
  * instead of the sum.  Async like cbx_synchronise; cbx_wait / the step
  * event cover the downloads.  The reference has no such call (its `push`
  * argument is unused, executioncontext.c:2264); update model WORKER runs
- * the three calls unpipelined.                                            */
+ * the three calls unpipelined, and so do elastic averaging and
+ * POLYAK_RUPPERT.                                                         */
 int cbx_synchronise_staged (cbx_context *ctx, int first, int clock, int autotune, int buckets);
 /* TheGPU.unlockAny() GPU.c:1142-1149 -> modelmanager.c:233-245           */
 int cbx_unlock_any (cbx_context *ctx);
@@ -314,7 +343,12 @@ int cbx_replica_set_disabled (cbx_context *ctx, int id, int flag);
  * stream, to be all-reduced and applied at the next barrier.  Under
  * DEFAULT it is crossbowKernelOptimiserDefault (default.cu:3-131): the
  * replica and its device's base model take the same step, in one pass on
- * the sync stream (the task stream waits for it).                       */
+ * the sync stream (the task stream waits for it).  Elastic averaging
+ * (SYNCHRONOUSEAMSGD with cbx_set_elastic_average) keeps the SMA step: the
+ * reference's optimisers/synchronouseamsgd.cu is the same call sequence.
+ * POLYAK_RUPPERT has no step here (CBX_ERR_UNSUPPORTED): the reference's
+ * optimisers/polyakruppert.cu is a stub, so the caller brings its own local
+ * step and updates the replica's data itself.                           */
 int cbx_replica_optimise (cbx_context *ctx, int id, int task, void *stream);
 /* Entries in local device `local`'s table of deferred task-stream waits
  * (see cbx_replica_optimise; at most 64). */
@@ -422,6 +456,14 @@ int cbx_set_barrier_kernel_config (cbx_context *ctx, int block, int unroll, int 
  * sma.c:135-183: 3 reads + 2 writes per element): block 64..256, unroll 1,
  * 2 or 4, occupancy cap as above.  Default 64 / 2 / auto.                 */
 int cbx_set_apply_kernel_config (cbx_context *ctx, int block, int unroll, int waves_per_cu);
+/* Launch geometry of the fused and accumulate-only kernels of the
+ * elastic-averaging and Polyak-Ruppert barriers (R + 1 or 2R + 1 reads,
+ * R + 1 or R + 2 writes per element): block 64..256, unroll 1, 2 or 4,
+ * occupancy cap as above.  Default 64 / 1 / auto (4 waves per CU at R = 8,
+ * measured: scripts/bench_averaging.py --sweep).  Their apply kernel at
+ * G > 1 follows cbx_set_apply_kernel_config, and all of them the load/store
+ * policy of cbx_set_kernel_config.                                         */
+int cbx_set_averaging_kernel_config (cbx_context *ctx, int block, int unroll, int waves_per_cu);
 /* Bucketed pipeline for G > 1: kernel A / all-reduce / kernel B per bucket
  * of `bucket_elements` floats; 0 (default) = 8 buckets when G > 1, one at
  * G = 1; a value >= n = one bucket, all in order on the sync stream.  With
