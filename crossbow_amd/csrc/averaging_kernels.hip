@@ -26,6 +26,74 @@
 namespace cbx {
 namespace {
 
+// Buffers the caller owns (the sma.c seam, sma_seam.hip) hold exactly n
+// floats.  Their last elements [a.tail_lo, a.tail_hi) go to the first
+// a.tail_blocks workgroups of the same launch (TAIL instantiations), one float
+// per lane, as in the SMA kernels (sma_tail_elem, sma_kernels.hip): the fma
+// sequence per element, the chunked replica walk and the three Polyak-Ruppert
+// rules are those of the float4 path below.
+template <int MODEL, int PHASE, bool LAST>
+__device__ __forceinline__ void averaging_tail_elem(const AvgArgs &a) {
+  const int64_t i = a.tail_lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.tail_hi) return;
+  float *z = reinterpret_cast<float *>(a.z);
+  float z0 = z[i];
+  float acc;
+  if constexpr (PHASE == 2) {
+    acc = reinterpret_cast<const float *>(a.D)[i];
+  } else {
+    // polyakruppert.c:72: with alpha == 0 the replicas are read, never written
+    const bool move = MODEL != kPolyak || a.alpha != 0.0f;
+    acc = 0.0f;  // synchronouseamsgd.c:43, polyakruppert.c:43
+    // every load of a chunk issued before its first store (sma_tail_elem)
+    for (int c = 0; c < a.nrep; c += kChunk) {
+      [[maybe_unused]] float sv[kChunk];
+      float wv[kChunk];
+#pragma unroll
+      for (int r = 0; r < kChunk; ++r) {
+        if (c + r < a.nrep) {
+          if constexpr (MODEL == kElasticS) sv[r] = reinterpret_cast<const float *>(a.s[c + r])[i];
+          wv[r] = reinterpret_cast<const float *>(a.w[c + r])[i];
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < kChunk; ++r) {
+        if (c + r < a.nrep) {
+          float w1;
+          if constexpr (MODEL == kPolyak) {
+            acc = fmaf(a.scale, wv[r], acc);           // polyakruppert.c:51-56
+            const float d = fmaf(-1.0f, z0, wv[r]);    // :63-69
+            w1 = fmaf(-a.alpha, d, wv[r]);             // :72-79
+          } else {
+            const float d = fmaf(-1.0f, z0, MODEL == kElasticS ? sv[r] : wv[r]);  // synchronouseamsgd.c:55-61, :181-192
+            w1 = fmaf(-a.alpha, d, wv[r]);             // :64-69
+            acc = fmaf(a.alpha, d, acc);               // :72-77
+          }
+          // a flagged replica takes z below (fused) or in the apply phase
+          if (move && !(MODEL == kPolyak && ((a.copy_mask >> (c + r)) & 1ull)))
+            reinterpret_cast<float *>(a.w[c + r])[i] = w1;
+        }
+      }
+    }
+    if constexpr (PHASE == 1) {
+      reinterpret_cast<float *>(a.acc)[i] = acc;
+      return;
+    }
+  }
+  if constexpr (MODEL == kPolyak) {
+    const float L = fmaf(-1.0f, z0, acc);  // polyakruppert.c:98-104
+    if constexpr (LAST) reinterpret_cast<float *>(a.last)[i] = L;
+    z0 = fmaf(a.running, L, z0);  // :107-112
+  } else {
+    z0 = fmaf(1.0f, acc, z0);  // synchronouseamsgd.c:85-90
+  }
+  z[i] = z0;
+  if constexpr (MODEL == kPolyak) {
+    for (uint64_t m = a.copy_mask; m != 0; m &= m - 1)
+      reinterpret_cast<float *>(a.w[__builtin_ctzll(m)])[i] = z0;  // polyakruppert.c:122-137
+  }
+}
+
 // ---------------------------------------------------------------------------
 // One kernel for {kElasticW, kElasticS, kPolyak} x PHASE {0 fused, 1
 // accumulate-only, 2 apply}.  R >= 1 replicas fully unrolled (R <= kChunk);
@@ -46,16 +114,23 @@ namespace {
 //   z   = fma(1/(clock+1), L, z)       :107-112
 //   w_i = z                            :122-137 (only replicas whose copy flag is raised)
 // ---------------------------------------------------------------------------
-template <int MODEL, int PHASE, int R, bool LAST, int P, int U>
+template <int MODEL, int PHASE, int R, bool LAST, int P, bool TAIL, int U>
 __global__ __launch_bounds__(256) void averaging_kernel(const AvgArgs a) {
   constexpr int RR = (R > 0) ? R : kChunk;
   constexpr int RS = (MODEL == kElasticS) ? RR : 1;
-  const uint32_t trip = gridDim.x * blockDim.x * U;
+  if constexpr (TAIL) {
+    if (blockIdx.x < (uint32_t)a.tail_blocks) {
+      averaging_tail_elem<MODEL, PHASE, LAST>(a);
+      return;
+    }
+  }
+  const uint32_t tb = TAIL ? (uint32_t)a.tail_blocks : 0u;
+  const uint32_t trip = (gridDim.x - tb) * blockDim.x * U;
   const uint32_t n4 = (uint32_t)a.n4;
   const v4f al = a.alpha, nal = -a.alpha, sc = a.scale, ru = a.running, one = 1.0f, mone = -1.0f;
   // polyakruppert.c:72: with alpha == 0 the replicas are read, never written
   const bool move = MODEL != kPolyak || a.alpha != 0.0f;
-  for (uint32_t base = first_elem<U>(); base < n4; base += trip) {
+  for (uint32_t base = first_elem<U>(blockIdx.x - tb); base < n4; base += trip) {
     v4f zv[U], acc[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -153,12 +228,18 @@ void stream_counts(int model, int phase, const AvgArgs &a, int *reads, int *writ
 }
 
 template <int MODEL, int PHASE, int R, bool LAST, int P>
-hipError_t avg_u(const AvgArgs &a, const LaunchConfig &cfg0, hipStream_t s, Timing t) {
-  const LaunchConfig cfg = small_launch_shape(cfg0, a.n4);
-  // every trip of every wave is whole: no bounds check sits in the kernel's loop
-  if (a.n4 <= 0 || a.n4 % kPadFloat4 != 0 || kPadFloat4 % ((int64_t)cfg.block * cfg.unroll) != 0)
+hipError_t avg_u(const AvgArgs &a0, const LaunchConfig &cfg0, hipStream_t s, Timing t) {
+  const LaunchConfig cfg = small_launch_shape(cfg0, a0.n4);
+  const bool tail = a0.tail_hi > a0.tail_lo;
+  // Every wave's chunk (64 lanes x unroll float4s, first_elem) is whole, so no
+  // bounds check sits in the kernel's loop.  The context's padded buffers are
+  // whole kPadFloat4s; the bulk of a caller-owned buffer is whole chunks only
+  // (e.g. 1,280 float4s), and may be empty when a tail is all there is.
+  if (cfg.block <= 0 || cfg.block % 64 != 0 || cfg.unroll < 1 || a0.n4 < 0 || a0.n4 % (64ll * cfg.unroll) != 0 ||
+      (a0.n4 == 0 && !tail))
     return hipErrorInvalidValue;
-  const dim3 g = grid_for(a.n4, cfg);
+  dim3 g = a0.n4 > 0 ? grid_for(a0.n4, cfg) : dim3(0);
+  const AvgArgs &a = a0;
   int reads = 0, writes = 0;
   stream_counts(MODEL, PHASE, a, &reads, &writes);
   // Auto occupancy: the apply phase as SMA's kernel B (kStreamsPerCU), the
@@ -171,12 +252,28 @@ hipError_t avg_u(const AvgArgs &a, const LaunchConfig &cfg0, hipStream_t s, Timi
     cap.waves_per_cu = w < 2 ? 2 : (w > 12 ? 12 : w);
   }
   const unsigned lds = lds_for_occupancy(cap, reads, writes, g.x);
+  if (tail) {  // caller-owned buffers: the tail rides the same launch, in front
+    if constexpr (P != 1) {
+      return hipErrorInvalidValue;
+    } else {
+      AvgArgs b = a0;
+      b.tail_blocks = (int)((b.tail_hi - b.tail_lo + cfg.block - 1) / cfg.block);
+      g.x += (unsigned)b.tail_blocks;
+      if (cfg.unroll == 2)
+        hipExtLaunchKernelGGL((averaging_kernel<MODEL, PHASE, R, LAST, P, true, 2>), g, dim3(cfg.block), lds, s, t.start, t.stop, 0, b);
+      else if (cfg.unroll == 1)
+        hipExtLaunchKernelGGL((averaging_kernel<MODEL, PHASE, R, LAST, P, true, 1>), g, dim3(cfg.block), lds, s, t.start, t.stop, 0, b);
+      else
+        return hipErrorInvalidValue;
+      return hipGetLastError();
+    }
+  }
   if (cfg.unroll == 4)
-    hipExtLaunchKernelGGL((averaging_kernel<MODEL, PHASE, R, LAST, P, 4>), g, dim3(cfg.block), lds, s, t.start, t.stop, 0, a);
+    hipExtLaunchKernelGGL((averaging_kernel<MODEL, PHASE, R, LAST, P, false, 4>), g, dim3(cfg.block), lds, s, t.start, t.stop, 0, a);
   else if (cfg.unroll == 2)
-    hipExtLaunchKernelGGL((averaging_kernel<MODEL, PHASE, R, LAST, P, 2>), g, dim3(cfg.block), lds, s, t.start, t.stop, 0, a);
+    hipExtLaunchKernelGGL((averaging_kernel<MODEL, PHASE, R, LAST, P, false, 2>), g, dim3(cfg.block), lds, s, t.start, t.stop, 0, a);
   else
-    hipExtLaunchKernelGGL((averaging_kernel<MODEL, PHASE, R, LAST, P, 1>), g, dim3(cfg.block), lds, s, t.start, t.stop, 0, a);
+    hipExtLaunchKernelGGL((averaging_kernel<MODEL, PHASE, R, LAST, P, false, 1>), g, dim3(cfg.block), lds, s, t.start, t.stop, 0, a);
   return hipGetLastError();
 }
 

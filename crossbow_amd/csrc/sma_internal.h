@@ -347,12 +347,14 @@ struct AvgArgs {
   v4f *last;                   // kPolyak: base->last, left holding acc - z (may be null)
   v4f *acc;                    // accumulate-only phase: its output
   const v4f *D;                // apply phase: the all-reduced acc
-  int64_t n4;                  // float4s in the launch's range (multiple of kPadFloat4)
+  int64_t n4;                  // float4s in the launch's range (whole 64 x unroll chunks; the context's: kPadFloat4s)
   uint64_t copy_mask;          // kPolyak: bit r set = a.w[r] becomes z (its copy flag is raised)
   float alpha;                 // conf->alpha
   float scale;                 // kPolyak: 1 / replicas (polyakruppert.c:15)
   float running;               // kPolyak: 1 / (clock + 1) (:16)
   int nrep;                    // locked replicas on this device, id order
+  int64_t tail_lo, tail_hi;    // caller-owned buffers: elements past the last whole trip (see SmaArgs)
+  int tail_blocks;
 };
 // One device (and not forced to split): the whole step in one pass.
 hipError_t launch_averaging_fused(AvgModel m, const AvgArgs &a, const LaunchConfig &cfg, hipStream_t stream,

@@ -6,6 +6,9 @@
 //   crossbowKernelOptimiserSMA (kernels/optimisers/sma.cu:3-100)
 //   crossbowSynchronisationSynchronousSGD (synch/synchronoussgd.c:13-106)
 //   crossbowKernelOptimiserSynchronousSGD (kernels/optimisers/synchronoussgd.cu:3-56)
+//   crossbowSynchronisationSynchronousElasticAveragingSGD
+//     (synch/synchronouseamsgd.c:307 -> :5-101, :106-305)
+//   crossbowSynchronisationPolyakRuppert (synch/polyakruppert.c:319 -> :5-138, :140-317)
 //   crossbowCudnnBatchNormParamsSynchroniseEstimatedMeanAndVariable
 //     (cudnn/cudnnbatchnormparams.c:157-222)
 //
@@ -88,6 +91,18 @@ struct cbx_sma_plan {
   cbx::LaunchConfig cfg;
   cbx::LaunchConfig apply_cfg = cbx::sma_apply_launch_config();
   cbx::LaunchConfig ssgd_apply_cfg = cbx::ssgd_apply_launch_config();
+  cbx::LaunchConfig avg_cfg = cbx::averaging_launch_config();  // cbx_ea_plan_step / cbx_pr_plan_step: fused and kernel A
+  // cbx_sma_plan_set_timing: the one-rank fused launches stamp their own start
+  // and stop into a ring of kTimedSteps event pairs (no marker packets).
+  static constexpr int kTimedSteps = 256;
+  bool timing = false;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> timed;
+  int64_t timed_steps = 0;  // launches stamped since timing was switched on
+  cbx::Timing next_timing() {
+    if (!timing) return {};
+    const auto &e = timed[(size_t)(timed_steps++ % kTimedSteps)];
+    return {e.first, e.second};
+  }
 };
 
 namespace {
@@ -107,9 +122,173 @@ int ensure_pipeline(cbx_sma_plan *p, int64_t nb) {
   return CBX_OK;
 }
 
+// The elastic-averaging (synch/synchronouseamsgd.c:5-101, :106-305) and
+// Polyak-Ruppert (synch/polyakruppert.c:5-138, :140-317) barriers over the
+// caller's buffers: the context's averaging_step (sync_steps.hip) with the
+// plan's scratch for acc / D.  One rank: the fused kernel.  Several: kernel A,
+// the all-reduce of acc into D, kernel B, bucketed as cbx_sma_plan_step is
+//   stream      : A(0) A(1) [wait r(0)] B(0) A(2) [wait r(1)] B(1) ...
+//   comm_stream : [wait a(0)] AR(0) [wait a(1)] AR(1) ...
+// with no control block; the tail rides the last bucket.  Everything is
+// validated before the first launch.  Returns the raised copy flags among the
+// locked replicas from `first` on (Polyak-Ruppert; 0 for elastic averaging).
+int averaging_plan_step(cbx_sma_plan *p, const char *what, bool polyak, void *const *streams, float *const *z,
+                        float *const *last, int nreplicas, const int *replica_device, float *const *w,
+                        const float *const *s, const int *locked, const int *copy, float alpha, int clock,
+                        int first) {
+  if (!p) return fail(CBX_ERR_INVALID, "null plan");
+  const int G = (int)p->devs.size();
+  // synchronouseamsgd.c:55 reads the replica's data on one device, :184 its snapshot on several
+  const cbx::AvgModel model = polyak ? cbx::kPolyak : (p->ranks > 1 ? cbx::kElasticS : cbx::kElasticW);
+  const bool snap = model == cbx::kElasticS;
+  if (!streams || !z || nreplicas < 0 ||
+      (nreplicas > 0 && (!replica_device || !w || !locked || (polyak && !copy) || (snap && !s))))
+    return fail(CBX_ERR_INVALID, "%s: missing arguments", what);
+  if (polyak && clock < 0) return fail(CBX_ERR_INVALID, "%s: clock %d is negative", what, clock);  // polyakruppert.c:16
+  if (first < 0 || first > nreplicas) return fail(CBX_ERR_INVALID, "first replica %d out of range", first);
+  std::vector<cbx::AvgArgs> args(G);
+  for (int k = 0; k < G; ++k) {
+    std::memset(&args[k], 0, sizeof(cbx::AvgArgs));
+    float *l = polyak && last ? last[k] : nullptr;  // model.c:116-120: base->last may not exist
+    if (!z[k] || !aligned16(z[k]) || !aligned16(l))
+      return fail(CBX_ERR_INVALID, "device %d: base buffers must be non-null and 16-byte aligned", k);
+  }
+  int copies = 0;
+  for (int id = first; id < nreplicas; ++id) {
+    if (!locked[id]) continue;
+    const int k = replica_device[id];
+    if (k < 0 || k >= G) return fail(CBX_ERR_INVALID, "replica %d on device %d of %d", id, k, G);
+    if (!w[id] || !aligned16(w[id]) || (snap && (!s[id] || !aligned16(s[id]))))
+      return fail(CBX_ERR_INVALID, "replica %d: buffers must be non-null and 16-byte aligned", id);
+    cbx::AvgArgs &a = args[k];
+    if (a.nrep >= cbx::kMaxReplicas)
+      return fail(CBX_ERR_UNSUPPORTED, "more than %d locked replicas on one device", cbx::kMaxReplicas);
+    if (snap) a.s[a.nrep] = reinterpret_cast<const cbx::v4f *>(s[id]);
+    a.w[a.nrep] = reinterpret_cast<cbx::v4f *>(w[id]);
+    if (polyak && copy[id]) {  // polyakruppert.c:126
+      a.copy_mask |= 1ull << a.nrep;
+      ++copies;
+    }
+    ++a.nrep;
+  }
+  for (int k = 0; k < G; ++k) {
+    auto &d = p->devs[k];
+    cbx::AvgArgs &a = args[k];
+    a.z = reinterpret_cast<cbx::v4f *>(z[k]);
+    a.last = polyak && last ? reinterpret_cast<cbx::v4f *>(last[k]) : nullptr;
+    a.acc = reinterpret_cast<cbx::v4f *>(d.acc_ctrl + cbx::kCtrlFloats);
+    a.D = reinterpret_cast<const cbx::v4f *>(d.D_ctrl + cbx::kCtrlFloats);
+    a.alpha = alpha;
+    if (polyak) {
+      a.scale = (float)(1.0 / (double)(float)nreplicas);      // polyakruppert.c:15
+      a.running = (float)(1.0 / (double)(float)(clock + 1));  // :16
+    }
+  }
+  // Bucket b of device k: `len4` float4s from `start4`, plus, on the launch
+  // that covers the buffers' end, the elements past the last whole chunk.
+  auto range = [&](const cbx::AvgArgs &a, int64_t start4, int64_t len4, bool tail) {
+    cbx::AvgArgs b = a;
+    for (int r = 0; r < a.nrep; ++r) {
+      if (a.s[r]) b.s[r] = a.s[r] + start4;
+      b.w[r] = a.w[r] + start4;
+    }
+    b.z = a.z + start4;
+    if (a.last) b.last = a.last + start4;
+    b.acc = a.acc + start4;
+    b.D = a.D + start4;
+    b.n4 = len4;
+    if (tail) {
+      b.tail_lo = (p->n4b - start4) * 4;
+      b.tail_hi = p->n - start4 * 4;
+    }
+    return b;
+  };
+  if (p->ranks == 1) {
+    auto &d = p->devs[0];
+    HIP_TRY(hipSetDevice(d.hip_id));
+    cbx::LaunchConfig cfg = p->avg_cfg;
+    cfg.num_cus = d.num_cus;
+    HIP_TRY(cbx::launch_averaging_fused(model, range(args[0], 0, p->n4b, true), cfg,
+                                        static_cast<hipStream_t>(streams[0]), p->next_timing()));
+    return copies;
+  }
+  const int64_t pad = cbx::kPadFloat4;
+  int64_t nb = p->buckets > 0 ? p->buckets : kDefaultBuckets;
+  int64_t b4 = p->n4b;
+  if (nb > 1 && p->n4b > 0) b4 = ((p->n4b + nb - 1) / nb + pad - 1) / pad * pad;
+  nb = b4 > 0 ? (p->n4b + b4 - 1) / b4 : 1;
+  const bool piped = nb > 1;
+  if (piped) TRY(ensure_pipeline(p, nb));
+  auto start_of = [&](int64_t b) { return b * b4; };
+  auto len_of = [&](int64_t b) { return std::min(b4, p->n4b - b * b4); };
+  auto apply = [&](int64_t b) -> int {
+    for (int k = 0; k < G; ++k) {
+      auto &d = p->devs[k];
+      hipStream_t st = static_cast<hipStream_t>(streams[k]);
+      HIP_TRY(hipSetDevice(d.hip_id));
+      if (piped) HIP_TRY(hipStreamWaitEvent(st, d.ev_r[b], 0));
+      cbx::LaunchConfig cfg = p->apply_cfg;
+      cfg.num_cus = d.num_cus;
+      HIP_TRY(cbx::launch_averaging_apply(model, range(args[k], start_of(b), len_of(b), b == nb - 1), cfg, st));
+    }
+    return CBX_OK;
+  };
+  for (int64_t b = 0; b < nb; ++b) {
+    for (int k = 0; k < G; ++k) {
+      auto &d = p->devs[k];
+      hipStream_t st = static_cast<hipStream_t>(streams[k]);
+      HIP_TRY(hipSetDevice(d.hip_id));
+      cbx::LaunchConfig cfg = p->avg_cfg;
+      cfg.num_cus = d.num_cus;
+      HIP_TRY(cbx::launch_averaging_accumulate(model, range(args[k], start_of(b), len_of(b), b == nb - 1), cfg, st));
+      if (piped) {
+        HIP_TRY(hipEventRecord(d.ev_a[b], st));
+        HIP_TRY(hipStreamWaitEvent(d.comm_stream, d.ev_a[b], 0));
+      }
+    }
+    NCCL_TRY(ncclGroupStart());
+    for (int k = 0; k < G; ++k) {
+      auto &d = p->devs[k];
+      HIP_TRY(hipSetDevice(d.hip_id));
+      const int64_t lo_f = start_of(b) * 4;
+      const int64_t hi_f = b == nb - 1 ? p->n : (start_of(b) + len_of(b)) * 4;
+      NCCL_TRY(ncclAllReduce(d.acc_ctrl + cbx::kCtrlFloats + lo_f, d.D_ctrl + cbx::kCtrlFloats + lo_f,
+                             (size_t)(hi_f - lo_f), ncclFloat, ncclSum, d.comm,
+                             piped ? d.comm_stream : static_cast<hipStream_t>(streams[k])));
+    }
+    NCCL_TRY(ncclGroupEnd());
+    if (piped) {
+      for (int k = 0; k < G; ++k) {
+        auto &d = p->devs[k];
+        HIP_TRY(hipSetDevice(d.hip_id));
+        HIP_TRY(hipEventRecord(d.ev_r[b], d.comm_stream));
+      }
+      if (b >= 1) TRY(apply(b - 1));
+    }
+  }
+  TRY(apply(nb - 1));
+  return copies;
+}
+
 }  // namespace
 
 extern "C" {
+
+int cbx_ea_plan_step(cbx_sma_plan *p, void *const *streams, float *const *z, int nreplicas, const int *replica_device,
+                     float *const *w, const float *const *s, const int *locked, float alpha, int first) {
+  TraceRange trace("cbx_ea_plan_step");
+  const int rc = averaging_plan_step(p, "cbx_ea_plan_step", false, streams, z, nullptr, nreplicas, replica_device, w,
+                                     s, locked, nullptr, alpha, 0, first);
+  return rc < 0 ? rc : CBX_OK;
+}
+
+int cbx_pr_plan_step(cbx_sma_plan *p, void *const *streams, float *const *z, float *const *last, int nreplicas,
+                     const int *replica_device, float *const *w, const int *locked, const int *copy, float alpha,
+                     int clock, int first) {
+  TraceRange trace("cbx_pr_plan_step");
+  return averaging_plan_step(p, "cbx_pr_plan_step", true, streams, z, last, nreplicas, replica_device, w, nullptr,
+                             locked, copy, alpha, clock, first);
+}
 
 int cbx_sma_plan_free(cbx_sma_plan *p) {
   if (!p) return CBX_OK;
@@ -125,8 +304,41 @@ int cbx_sma_plan_free(cbx_sma_plan *p) {
     for (hipEvent_t e : d.ev_r) (void)hipEventDestroy(e);
     if (d.comm_stream) (void)hipStreamDestroy(d.comm_stream);
   }
+  for (auto &e : p->timed) {
+    (void)hipEventDestroy(e.first);
+    (void)hipEventDestroy(e.second);
+  }
   delete p;
   return CBX_OK;
+}
+
+int cbx_sma_plan_set_timing(cbx_sma_plan *p, int on) {
+  if (!p) return fail(CBX_ERR_INVALID, "null plan");
+  if (on && p->timed.empty()) {
+    HIP_TRY(hipSetDevice(p->devs[0].hip_id));
+    for (int k = 0; k < cbx_sma_plan::kTimedSteps; ++k) {
+      hipEvent_t a, b;
+      HIP_TRY(hipEventCreate(&a));
+      HIP_TRY(hipEventCreate(&b));
+      p->timed.emplace_back(a, b);
+    }
+  }
+  p->timing = on != 0;
+  p->timed_steps = 0;
+  return CBX_OK;
+}
+
+int cbx_sma_plan_timing_history(cbx_sma_plan *p, float *ms, int count) {
+  if (!p) return fail(CBX_ERR_INVALID, "null plan");
+  if (!ms || count < 0) return fail(CBX_ERR_INVALID, "cbx_sma_plan_timing_history: bad arguments");
+  const int64_t have = std::min<int64_t>(p->timed_steps, cbx_sma_plan::kTimedSteps);
+  const int64_t take = std::min<int64_t>(count, have);
+  for (int64_t k = 0; k < take; ++k) {  // oldest first
+    const auto &e = p->timed[(size_t)((p->timed_steps - take + k) % cbx_sma_plan::kTimedSteps)];
+    HIP_TRY(hipEventSynchronize(e.second));
+    HIP_TRY(hipEventElapsedTime(&ms[k], e.first, e.second));
+  }
+  return (int)take;
 }
 
 int cbx_sma_plan_create(cbx_sma_plan **out, const int *devices, int ndevices, long long elements,
@@ -265,7 +477,7 @@ int cbx_sma_plan_step(cbx_sma_plan *p, void *const *streams, float *const *z, fl
     HIP_TRY(hipSetDevice(d.hip_id));
     cbx::LaunchConfig cfg = p->cfg;
     cfg.num_cus = d.num_cus;
-    HIP_TRY(cbx::launch_sma_fused(with_tail(args[0], 0), mom, copies_total > 0, cfg, st));
+    HIP_TRY(cbx::launch_sma_fused(with_tail(args[0], 0), mom, copies_total > 0, cfg, st, p->next_timing()));
     return copies_total > 0 ? 1 : 0;
   }
   // G > 1: kernel A, the grouped all-reduce of the control block + acc

@@ -2,7 +2,9 @@
 the SMA step and the replica optimiser step over device buffers the caller
 owns, for a Crossbow build that keeps its own model manager and replaces only
 ``crossbowSynchronisationSMA`` (clib-multigpu/synch/sma.c:233-248) and
-``crossbowKernelOptimiserSMA`` (kernels/optimisers/sma.cu:3-100).
+``crossbowKernelOptimiserSMA`` (kernels/optimisers/sma.cu:3-100), and in the
+same way the synchronous-SGD, elastic-averaging (synch/synchronouseamsgd.c)
+and Polyak-Ruppert (synch/polyakruppert.c) barriers.
 
 Pointers and streams are plain integers (``tensor.data_ptr()``,
 ``torch.cuda.Stream().cuda_stream``, or raw ``hipMalloc`` results).  Torch-free:
@@ -84,6 +86,27 @@ class SmaPlan:
             len(replicas), _ints([r[0] for r in replicas]), _ptrs([r[1] for r in replicas]),
             _ints([r[2] for r in replicas]), ctypes.c_float(momentum), wpc, first), "cbx_ssgd_plan_step")
 
+    def elastic_step(self, streams: Sequence[int], z: Sequence[int],
+                     replicas: Sequence[Tuple[int, int, Optional[int], int]], alpha: float, first: int = 0) -> None:
+        """One elastic-averaging barrier (``cbx_ea_plan_step``).  ``replicas[id]``
+        = (device index, w, s, locked); ``s`` may be None (0) with one rank,
+        where the difference is taken from ``w``."""
+        s = [r[2] for r in replicas]
+        _raise(self.lib, self.lib.cbx_ea_plan_step(
+            self._p, _ptrs(streams), _ptrs(z), len(replicas), _ints([r[0] for r in replicas]),
+            _ptrs([r[1] for r in replicas]), _ptrs(s) if any(s) else None, _ints([r[3] for r in replicas]),
+            ctypes.c_float(alpha), first), "cbx_ea_plan_step")
+
+    def polyak_step(self, streams: Sequence[int], z: Sequence[int], last: Optional[Sequence[Optional[int]]],
+                    replicas: Sequence[Tuple[int, int, int, int]], alpha: float, clock: int, first: int = 0) -> int:
+        """One Polyak-Ruppert barrier (``cbx_pr_plan_step``).  ``replicas[id]`` =
+        (device index, w, locked, copy).  Returns how many locked replicas from
+        ``first`` on had ``copy`` raised and now equal their device's z."""
+        return _raise(self.lib, self.lib.cbx_pr_plan_step(
+            self._p, _ptrs(streams), _ptrs(z), _ptrs(last) if last is not None else None, len(replicas),
+            _ints([r[0] for r in replicas]), _ptrs([r[1] for r in replicas]), _ints([r[2] for r in replicas]),
+            _ints([r[3] for r in replicas]), ctypes.c_float(alpha), clock, first), "cbx_pr_plan_step")
+
     def average_batchnorm(self, elements: Sequence[int], mean: Sequence[int], variance: Sequence[int],
                           updated: Sequence[int]) -> None:
         """BN running-statistics averaging; ``mean``/``variance``/``updated`` are
@@ -121,6 +144,17 @@ class SmaPlan:
     def set_buckets(self, buckets: int) -> None:
         """G > 1: buckets of the all-reduce pipeline (0 = default 8, 1 = in order)."""
         _raise(self.lib, self.lib.cbx_sma_plan_set_buckets(self._p, buckets), "cbx_sma_plan_set_buckets")
+
+    def set_timing(self, on: bool) -> None:
+        """One rank: every step's fused launch stamps its own start and stop."""
+        _raise(self.lib, self.lib.cbx_sma_plan_set_timing(self._p, 1 if on else 0), "cbx_sma_plan_set_timing")
+
+    def timing_history(self, count: int):
+        """Kernel ms of the last ``count`` (at most 256) timed steps, oldest first."""
+        buf = (ctypes.c_float * max(1, count))()
+        got = _raise(self.lib, self.lib.cbx_sma_plan_timing_history(self._p, buf, count),
+                     "cbx_sma_plan_timing_history")
+        return [buf[k] for k in range(got)]
 
     def free(self) -> None:
         if self._p:

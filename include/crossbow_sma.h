@@ -650,7 +650,10 @@ int cbx_bench_copy (cbx_context *ctx, size_t bytes, int iters, float *gbps);
  *       -> cbx_sma_plan_step
  *   crossbowKernelOptimiserSMA (kernels/optimisers/sma.cu:3-100)
  *       -> cbx_sma_optimise_buffers
- * (INTEGRATION.md section 3 shows both bodies).  Buffers hold exactly
+ * and, further down, the synchronous-SGD pair (cbx_ssgd_plan_step,
+ * cbx_ssgd_accumulate_buffers), the elastic-averaging barrier
+ * (cbx_ea_plan_step) and the Polyak-Ruppert barrier (cbx_pr_plan_step)
+ * (INTEGRATION.md section 1b shows the bodies).  Buffers hold exactly
  * `elements` floats (no padding) and must be 16-byte aligned, as hipMalloc's
  * are.  Same kernels and arithmetic as the context path: bit-exact against
  * the oracle at one GPU and in rank order.  No context is involved.       */
@@ -671,6 +674,16 @@ int cbx_sma_plan_free (cbx_sma_plan *plan);
  * against its other work).  0 (default) = 8 buckets; 1 = the reference's
  * order, everything on the caller's stream.  Same results bit for bit.    */
 int cbx_sma_plan_set_buckets (cbx_sma_plan *plan, int buckets);
+/* Measurement aid for a one-rank plan (scripts/bench_averaging_seam.py):
+ * with `on`, the fused launch of every step (cbx_sma_plan_step,
+ * cbx_ea_plan_step, cbx_pr_plan_step) stamps its own start and stop, as the
+ * context's cbx_set_timing does, into a ring of the last 256 steps; no
+ * marker packet is added to the caller's stream.  Switching it (on or off)
+ * empties the ring.  cbx_sma_plan_timing_history waits for the last of them
+ * and writes the kernel times (ms) of the last `count` timed steps, oldest
+ * first; returns how many it wrote.  Steps with several ranks are not timed. */
+int cbx_sma_plan_set_timing (cbx_sma_plan *plan, int on);
+int cbx_sma_plan_timing_history (cbx_sma_plan *plan, float *ms, int count);
 /* One SMA step (sma.c:13-231), enqueued on the caller's streams, async:
  *   streams[k]        dev->modelSynchronisationStream of devices[k] (hipStream_t)
  *   z[k], last[k]     baseModels[k]->data->dev / ->last->dev (last may be NULL
@@ -751,6 +764,51 @@ int cbx_ssgd_plan_step (cbx_sma_plan *plan, void *const *streams, float *const *
                         const int *locked, float momentum, int wpc, int first);
 int cbx_ssgd_accumulate_buffers (void *stream, const float *w, float *g, float *acc, long long elements,
                                  float learning_rate, float weight_decay);
+/* The same seam for the two averaging barriers, over an existing plan: they
+ * share its acc / D scratch, communicators, comm stream, per-bucket events
+ * and cbx_sma_plan_set_buckets with the SMA and S-SGD steps, so any sequence
+ * of these steps on one plan is safe, one step at a time, streams[k] the
+ * same stream on every call (as for cbx_sma_plan_step).  Arguments named as
+ * for cbx_sma_plan_step mean the same.  Locked replicas at or above `first`
+ * go in id order per device; more than 64 of them on one device is
+ * CBX_ERR_UNSUPPORTED.  One rank: one fused launch on the caller's stream.
+ * Several: kernel A, ncclAllReduce of acc into D, kernel B, bucketed as the
+ * S-SGD step (AR(k) on the plan's stream beside A(k+1), B(k) after it; 1
+ * bucket = everything in order on the caller's stream).  No control block
+ * travels with these steps.  Same kernels and arithmetic as the context's
+ * update models 3 (with cbx_set_elastic_average) and 6: the buffers' last
+ * elements, past the last whole float4 chunk, run one float per lane on
+ * extra workgroups of the same launches with the same fma sequence.
+ *
+ * crossbowSynchronisationSynchronousElasticAveragingSGD
+ * (synch/synchronouseamsgd.c:307 -> :5-101 on one device, :106-305 on
+ * several) -> cbx_ea_plan_step.  The difference d = x - z is taken from
+ * w[id] when the plan's communicator has one rank (:55) and from the
+ * snapshot s[id] = replicas[id]->diff->dev when it has several (:184); `s`
+ * may be NULL with one rank.  No momentum; the copy flags are not read.
+ * The task step kernels/optimisers/synchronouseamsgd.cu is, per element,
+ * what cbx_sma_optimise_buffers already runs (weight decay, scale, momentum,
+ * last, the snapshot into diff, apply): use it unchanged.
+ * Returns CBX_OK or an error.                                              */
+int cbx_ea_plan_step (cbx_sma_plan *plan, void *const *streams, float *const *z, int nreplicas,
+                      const int *replica_device, float *const *w, const float *const *s, const int *locked,
+                      float alpha, int first);
+/* crossbowSynchronisationPolyakRuppert (synch/polyakruppert.c:319 -> :5-138
+ * on one device, :140-317 on several) -> cbx_pr_plan_step.  The average is
+ * over p = nreplicas = modelmanager->size (:15): every replica of every
+ * rank, locked or not (a process passes the other ranks' replicas as
+ * unlocked).  last[k] = baseModels[k]->last->dev may be NULL (and `last`
+ * itself, model.c:116-120); where given it is left holding L = D - z
+ * (:98-104).  clock = the step's clock (:16), >= 0 or CBX_ERR_INVALID.
+ * With alpha == 0 the replicas are read and not written (:72).  A locked
+ * replica from `first` on whose copy[id] is raised becomes its device's new
+ * z (:122-137) and is not written before that; a request stays local to
+ * its device.  Returns the number of this process's such replicas (>= 0):
+ * the caller resets their _copy (:131).  Errors are negative.  The
+ * reference's task step optimisers/polyakruppert.cu is a stub.             */
+int cbx_pr_plan_step (cbx_sma_plan *plan, void *const *streams, float *const *z, float *const *last,
+                      int nreplicas, const int *replica_device, float *const *w, const int *locked,
+                      const int *copy, float alpha, int clock, int first);
 
 #ifdef __cplusplus
 }
