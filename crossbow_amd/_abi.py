@@ -83,6 +83,7 @@ SIGNATURES = {
     "cbx_set_model_work_per_clock": (_I, [_P, _I]),
     "cbx_set_update_model_type": (_I, [_P, _I]),
     "cbx_set_elastic_average": (_I, [_P, _I]),
+    "cbx_set_variable_learning_rates": (_I, [_P, _I]),
     "cbx_set_learning_rate_decay_policy_fixed": (_I, [_P, _F]),
     "cbx_set_learning_rate_decay_policy_inv": (_I, [_P, _F, _D, _D]),
     "cbx_set_learning_rate_decay_policy_step": (_I, [_P, _F, _D, _I]),
@@ -117,6 +118,7 @@ SIGNATURES = {
     "cbx_replica_clock": (_I, [_P, _I]),
     "cbx_replica_learning_rate": (_I, [_P, _I, _I, _FP]),
     "cbx_replica_optimise": (_I, [_P, _I, _I, _P]),
+    "cbx_replica_optimise_variables": (_I, [_P, _I, _I, _I, _P]),
     "cbx_replica_get_copy": (_I, [_P, _I]),
     "cbx_replica_set_copy": (_I, [_P, _I, _I]),
     "cbx_acquire_access": (_I, [_P, _IP]),
@@ -176,6 +178,8 @@ SIGNATURES = {
     "cbx_sma_plan_step": (_I, [_P, _PP, _PP, _PP, _I, _IP, _PP, _PP, _IP, _IP, _F, _F, _I]),
     "cbx_sma_plan_buffer_stats": (_I, [_P, _I, _P, _P, _PP, _I, _LLP, _I, _BS, _BS, _BS, _BS]),
     "cbx_sma_optimise_buffers": (_I, [_P, _P, _P, _P, _P, _c.c_longlong, _F, _F, _F]),
+    "cbx_sma_plan_set_variables": (_I, [_P, _LLP, _FP, _I]),
+    "cbx_sma_plan_optimise_variables": (_I, [_P, _I, _P, _P, _P, _P, _P, _F, _F, _F, _I, _I]),
     "cbx_sma_plan_average_batchnorm": (_I, [_P, _I, _IP, _PP, _PP, _IP]),
     "cbx_ssgd_plan_step": (_I, [_P, _PP, _PP, _PP, _PP, _I, _IP, _PP, _IP, _F, _I, _I]),
     "cbx_ssgd_accumulate_buffers": (_I, [_P, _P, _P, _P, _c.c_longlong, _F, _F]),

@@ -15,6 +15,7 @@
 //     (control block) instead of a host-side count;
 //   * errors return codes; the JNI shim turns them back into exit(1).
 #include "context_internal.h"
+#include "optimise_plan.h"
 
 using namespace cbx::host;
 
@@ -262,12 +263,36 @@ int cbx_set_model_variable_buffer(cbx_context *c, int id, int order, const void 
   return CBX_OK;
 }
 
+// The index in offset order of variable (id, order) of a model whose
+// variables tile its elements (c->var_bounds is filled), or -1.
+static int variable_index(cbx_context *c, int id, int order) {
+  if (c->var_bounds.empty()) return -1;
+  for (size_t k = 0; k < c->stats_vars.size(); ++k)
+    if (c->stats_vars[k].op == id && c->stats_vars[k].order == order) return (int)k;
+  return -1;
+}
+
 int cbx_set_model_variable_learning_rate_multiplier(cbx_context *c, int id, int order, float multiplier) {
   TRY(check_ctx(c));
   auto it = c->model.vars.find({id, order});
   if (it == c->model.vars.end()) return fail(CBX_ERR_INVALID, "model variable not found (id %d, order %d)", id, order);
   it->second.lr_multiplier = multiplier;
   if (multiplier != 1.0f) c->model.conf.irregular++;  // executioncontext.c:1602-1603
+  if (c->manager && !c->var_bounds.empty()) {
+    // After cbx_set_model_manager: a blocking re-upload.  Every device is
+    // drained first, so no step still in flight on any stream reads the table
+    // while it changes, and the next step enqueued finds the new value.
+    const int v = variable_index(c, id, order);
+    if (v >= 0) {
+      c->var_mult[(size_t)v] = multiplier;
+      for (Device &d : c->devs) {
+        if (!d.var_tables.mult) continue;
+        HIP_TRY(hipSetDevice(d.hip_id));
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(d.var_tables.mult + v, &multiplier, sizeof(float), hipMemcpyHostToDevice));
+      }
+    }
+  }
   return CBX_OK;
 }
 
@@ -379,6 +404,56 @@ int cbx_set_eamsgd_tau(cbx_context *c, int tau) {
 }
 
 // ---- model manager --------------------------------------------------------
+// The tables of the per-variable replica step (optimise_plan.h), built once
+// and uploaded to every local device; replicas added later use them too.  A
+// model whose variables do not tile its elements has no variable ranges: the
+// reason is kept for the calls that need them.
+static int build_variable_tables(cbx_context *c) {
+  ModelDef &m = c->model;
+  c->var_bounds.clear();
+  c->var_mult.clear();
+  c->op_vars.assign((size_t)m.ops, {});
+  c->var_refusal.clear();
+  if (m.vars.empty()) {
+    c->var_refusal = "the model was registered as raw bytes: it has no variables";
+    return CBX_OK;
+  }
+  for (const auto &e : m.vars)
+    if (e.second.bytes != e.second.elements * 4) {
+      char msg[200];
+      std::snprintf(msg, sizeof(msg),
+                    "variable (op %d, order %d) has a capacity of %lld bytes for %lld floats: the variables do not "
+                    "tile the model's elements",
+                    e.first.first, e.first.second, (long long)e.second.bytes, (long long)e.second.elements);
+      c->var_refusal = msg;
+      return CBX_OK;
+    }
+  // Every capacity is its shape's bytes, so the offsets are the running sum
+  // of the elements and c->stats_vars holds the variables in offset order.
+  const size_t V = c->stats_vars.size();
+  if (V != m.vars.size() || c->stats_vars[0].op < 0) return fail(CBX_ERR_STATE, "variables tile the model but were not listed");
+  std::vector<long long> elems(V);
+  for (size_t v = 0; v < V; ++v) elems[v] = c->stats_vars[v].elements;
+  cbx::OptimisePlan plan;
+  if (!cbx::build_optimise_plan(elems.data(), (int)V, c->n, &plan))
+    return fail(CBX_ERR_INVALID, "the variables of the model do not sum to its %lld elements", (long long)c->n);
+  c->var_mult.resize(V);
+  for (size_t v = 0; v < V; ++v) {
+    const cbx_context::StatsVar &sv = c->stats_vars[v];
+    c->var_mult[v] = m.vars.at({sv.op, sv.order}).lr_multiplier;
+    std::vector<int> &ov = c->op_vars[(size_t)sv.op];
+    if ((int)ov.size() < sv.order) ov.resize((size_t)sv.order, -1);
+    ov[(size_t)sv.order - 1] = (int)v;
+  }
+  for (Device &d : c->devs) {
+    HIP_TRY(hipSetDevice(d.hip_id));
+    HIP_TRY(cbx::var_tables_upload(d.var_tables, plan.chunks.data(), plan.chunks.size(), plan.bounds.data(),
+                                   c->var_mult.data(), (uint32_t)V));
+  }
+  c->var_bounds = plan.bounds;
+  return CBX_OK;
+}
+
 int cbx_set_model_manager(cbx_context *c, int replicas, int type) {
   TRY(check_ctx(c));
   if (c->manager) return fail(CBX_ERR_STATE, "model manager already created");
@@ -466,6 +541,7 @@ int cbx_set_model_manager(cbx_context *c, int replicas, int type) {
     d.step_event = d.synched;
     HIP_TRY(hipStreamSynchronize(d.stream));
   }
+  TRY(build_variable_tables(c));
   c->manager = true;
   return CBX_OK;
 }
@@ -1034,6 +1110,7 @@ static int ssgd_worker_step(cbx_context *c, Replica &r, Device &d, int task, hip
 }
 
 static int replica_optimise_impl(cbx_context *c, int id, int task, void *stream);
+static int replica_optimise_variables_impl(cbx_context *c, int id, int task, int op, void *stream);
 
 // Task threads call this while the collector thread may be enqueueing a
 // barrier.  The foreign-op counter is bumped on entry (check_replica) AND
@@ -1047,18 +1124,29 @@ int cbx_replica_optimise(cbx_context *c, int id, int task, void *stream) {
   return rc;
 }
 
-static int replica_optimise_impl(cbx_context *c, int id, int task, void *stream) {
-  TRY(check_replica(c, id, true));
-  Replica &r = *c->replicas[id];
-  Device &d = c->devs[r.local];
+int cbx_replica_optimise_variables(cbx_context *c, int id, int task, int op, void *stream) {
+  TraceRange trace("cbx_replica_optimise_variables");
+  const int rc = replica_optimise_variables_impl(c, id, task, op, stream);
+  if (c) c->foreign_ops.fetch_add(1, std::memory_order_release);
+  return rc;
+}
+
+int cbx_set_variable_learning_rates(cbx_context *c, int enable) {
+  TRY(check_ctx(c));
+  if (enable != 0 && enable != 1)
+    return fail(CBX_ERR_INVALID, "cbx_set_variable_learning_rates: %d is neither 0 nor 1", enable);
+  c->variable_rates = enable == 1;
+  return CBX_OK;
+}
+
+// Float ranges [lo, hi) of a replica's buffers.  nullptr: the whole model
+// with the solver's one rate (sma_optimise_kernel); else each range with the
+// rate of its variables (sma_optimise_variables_kernel), one launch each.
+using VarRanges = std::vector<std::pair<uint32_t, uint32_t>>;
+
+// crossbowKernelOptimiserSMA (sma.cu:3-100) on one replica, whole or ranged.
+static int sma_task_step(cbx_context *c, Replica &r, Device &d, int task, void *stream, const VarRanges *ranges) {
   SolverConf &conf = r.conf;
-  const int type = c->model.type;
-  if (type == CBX_UPDATE_WORKER)
-    return ssgd_worker_step(c, r, d, task, stream ? reinterpret_cast<hipStream_t>(stream) : d.stream);
-  if (type == CBX_UPDATE_DEFAULT)
-    return default_task_step(c, r, d, task, stream ? reinterpret_cast<hipStream_t>(stream) : d.stream);
-  if (type != CBX_UPDATE_SMA && type != CBX_UPDATE_SYNCHRONOUSEAMSGD)
-    return fail(CBX_ERR_UNSUPPORTED, "update model %d has no optimiser step in this library", type);
   if (conf.momentum > 0 && conf.momentumMethod == 1)
     return fail(CBX_ERR_UNSUPPORTED, "Nesterov's momentum has been disabled");  // sma.cu:46-48
   if (conf.momentum > 0 && !c->has_last)
@@ -1084,11 +1172,74 @@ static int replica_optimise_impl(cbx_context *c, int id, int task, void *stream)
   // The replica must not be updated while the last synchronise() still uses
   // it (the reference's forward kernels wait on replica->updated).
   if (st != d.stream && d.step_event) HIP_TRY(hipStreamWaitEvent(st, d.step_event, 0));
-  HIP_TRY(cbx::launch_sma_optimise(a, cfg, st, {}));
+  if (!ranges) {
+    HIP_TRY(cbx::launch_sma_optimise(a, cfg, st, {}));
+  } else {
+    cbx::VarOptArgs v;
+    std::memset(&v, 0, sizeof(v));
+    v.w = a.w;
+    v.g = a.g;
+    v.last = a.last;
+    v.s = a.s;
+    v.rate = a.rate;
+    v.momentum = a.momentum;
+    v.wd = a.wd;
+    for (const auto &range : *ranges) {
+      v.lo = range.first;
+      v.hi = range.second;
+      HIP_TRY(cbx::launch_sma_optimise_variables(d.var_tables, v, cfg, st, {}));
+    }
+  }
   // sma.cu:79-81: the synchronisation stream waits for the updated replica,
   // from its next use by the library on (flush_task_waits).
   if (st != d.stream && !c->fault_skip_task_wait) TRY(defer_task_wait(d, st));
   return CBX_OK;
+}
+
+static int replica_optimise_impl(cbx_context *c, int id, int task, void *stream) {
+  TRY(check_replica(c, id, true));
+  Replica &r = *c->replicas[id];
+  Device &d = c->devs[r.local];
+  const int type = c->model.type;
+  if (type == CBX_UPDATE_WORKER)
+    return ssgd_worker_step(c, r, d, task, stream ? reinterpret_cast<hipStream_t>(stream) : d.stream);
+  if (type == CBX_UPDATE_DEFAULT)
+    return default_task_step(c, r, d, task, stream ? reinterpret_cast<hipStream_t>(stream) : d.stream);
+  if (type != CBX_UPDATE_SMA && type != CBX_UPDATE_SYNCHRONOUSEAMSGD)
+    return fail(CBX_ERR_UNSUPPORTED, "update model %d has no optimiser step in this library", type);
+  // model.c:167: the multipliers count only when one of them is not 1
+  if (!c->variable_rates || c->model.conf.irregular <= 0) return sma_task_step(c, r, d, task, stream, nullptr);
+  if (!c->var_refusal.empty())
+    return fail(CBX_ERR_UNSUPPORTED, "cbx_replica_optimise with variable learning rates: %s", c->var_refusal.c_str());
+  const VarRanges whole(1, {0u, (uint32_t)c->n});
+  return sma_task_step(c, r, d, task, stream, &whole);
+}
+
+// crossbowStreamSynchronousEamsgdModelUpdate (stream.c:422-479): the step on
+// the variables of operator `op` only, orders 1..count.  Variables that are
+// neighbours in the buffer share a launch.
+static int replica_optimise_variables_impl(cbx_context *c, int id, int task, int op, void *stream) {
+  TRY(check_replica(c, id, true));
+  Replica &r = *c->replicas[id];
+  Device &d = c->devs[r.local];
+  const int type = c->model.type;
+  if (type != CBX_UPDATE_SMA && type != CBX_UPDATE_SYNCHRONOUSEAMSGD)
+    return fail(CBX_ERR_UNSUPPORTED, "update model %d has no per-operator optimiser step in this library", type);
+  if (op < 0 || op >= c->model.ops) return fail(CBX_ERR_INVALID, "operator %d out of range [0, %d)", op, c->model.ops);
+  if (!c->var_refusal.empty())
+    return fail(CBX_ERR_UNSUPPORTED, "cbx_replica_optimise_variables: %s", c->var_refusal.c_str());
+  if (c->model.count_per_op[(size_t)op] == 0) return CBX_OK;  // stream.c:499-501
+  std::vector<int> vars = c->op_vars[(size_t)op];
+  std::sort(vars.begin(), vars.end());
+  VarRanges ranges;
+  for (size_t k = 0; k < vars.size();) {
+    size_t e = k + 1;
+    while (e < vars.size() && vars[e] == vars[e - 1] + 1) ++e;
+    const uint32_t lo = c->var_bounds[(size_t)vars[k]], hi = c->var_bounds[(size_t)vars[e - 1] + 1];
+    if (lo < hi) ranges.push_back({lo, hi});
+    k = e;
+  }
+  return sma_task_step(c, r, d, task, stream, &ranges);
 }
 
 // ---- batch-norm running statistics (cudnn/cudnnbatchnormparams.c:157-222) --

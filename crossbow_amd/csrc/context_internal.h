@@ -269,7 +269,9 @@ struct Variable {
   int64_t offset_bytes;
   int64_t bytes;
   int64_t elements;
-  float lr_multiplier = 1.0f;  // variable.c; read only by per-variable optimisers, not by SMA's
+  // variable.c: read by the per-variable replica step (cbx_set_variable_learning_rates,
+  // cbx_replica_optimise_variables) when conf.irregular > 0, by nothing else
+  float lr_multiplier = 1.0f;
 };
 
 struct ModelDef {
@@ -389,6 +391,7 @@ struct Device {
   float *bn_scratch = nullptr;         // packed statistics, all-reduced
   size_t bn_scratch_bytes = 0;
   cbx::StatsScratch stats;             // cbx_model_stats: piece table, slab, results
+  cbx::VarTables var_tables;           // the per-variable replica step: chunk table, bounds, multipliers
   int num_cus = 256;
   // Arena: [base data][base gradient(ctrl+acc)][base diff(ctrl+D)][base last]
   //        then per replica [data][diff][last][gradient].
@@ -502,6 +505,17 @@ struct cbx_context {
     long long offset, elements;
   };
   std::vector<StatsVar> stats_vars;
+  // The per-variable replica step (cbx_set_variable_learning_rates,
+  // cbx_replica_optimise_variables).  Filled by cbx_set_model_manager when the
+  // variables tile the model's elements: their running offsets in floats
+  // (nvars + 1), their multipliers in offset order, and per operator the
+  // indices of its variables by order.  Otherwise var_refusal says why the
+  // model has no variable ranges (it names the variable).
+  bool variable_rates = false;
+  std::vector<uint32_t> var_bounds;
+  std::vector<float> var_mult;
+  std::vector<std::vector<int>> op_vars;
+  std::string var_refusal;
   // BN operators whose running statistics travel with the checkpoint
   // (executioncontext.c:2352-2364): op id -> per-local-device buffers.
   struct BnStats {
@@ -848,6 +862,7 @@ inline void close_device(Device &d) {
   if (d.bn_table) (void)hipFree(d.bn_table);
   if (d.bn_scratch) (void)hipFree(d.bn_scratch);
   cbx::stats_free(d.stats);
+  cbx::var_tables_free(d.var_tables);
   if (d.host) (void)hipHostFree(d.host);
   if (d.synched) (void)hipEventDestroy(d.synched);
   for (int k = 0; k < EV_COUNT; ++k)

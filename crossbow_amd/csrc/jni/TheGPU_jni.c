@@ -50,6 +50,7 @@ static jint fatal_or (int rc) {
  *   CBX_STAGING            zerocopy | dma       (cbx_set_staging_mode)
  *   CBX_ENQUEUE_THREADS    -1 | 0 | 1           (cbx_set_enqueue_threads)
  *   CBX_ELASTIC_AVERAGE    0 | 1                (cbx_set_elastic_average)
+ *   CBX_VARIABLE_RATES     0 | 1                (cbx_set_variable_learning_rates)
  * bench.py's warm-up tuner (crossbow_amd/dist.py) prints the values it
  * chose for a node in its JSON config. */
 static long long env_int (const char *name, int *present) {
@@ -100,6 +101,8 @@ static void configure_from_env (void) {
 	if (on) fatal_or (cbx_set_enqueue_threads (theGPU, v < -1 || v > 1 ? -2 : (int) v));
 	v = env_int ("CBX_ELASTIC_AVERAGE", &on);
 	if (on) fatal_or (cbx_set_elastic_average (theGPU, v < 0 || v > 1 ? -1 : (int) v));
+	v = env_int ("CBX_VARIABLE_RATES", &on);
+	if (on) fatal_or (cbx_set_variable_learning_rates (theGPU, v < 0 || v > 1 ? -1 : (int) v));
 }
 
 /* GPU.c:21-63.  Thread-count / core-offset arguments configure the reference's

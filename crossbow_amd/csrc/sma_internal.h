@@ -300,6 +300,45 @@ struct OptArgs {
   int tail_blocks;
 };
 hipError_t launch_sma_optimise(const OptArgs &a, const LaunchConfig &cfg, hipStream_t stream, Timing t = {});
+// The same step with a learning rate per variable (variable_rate_kernels.hip;
+// crossbowModelGetLearningRateForVariable, model.c:159-177, and the per-operator
+// crossbowStreamSynchronousEamsgdModelUpdate, stream.c:422-479): variable v
+// steps with r_v = rate * mult[v], one fp32 multiply, and otherwise exactly
+// launch_sma_optimise's sequence.  The sign convention is sma.cu's: g and
+// last hold the negative-rate values, so whole-model and ranged steps mix on
+// one replica (stream.c:455-467 scales by +rate and subtracts: the same w
+// bits, g and last of the opposite sign).  s = w is taken per element in the
+// ranged form too (the reference's incremental path predates the snapshot).
+// The tables (optimise_plan.h) live in one device allocation.
+struct VarTables {
+  uint32_t *chunks = nullptr;  // one entry per 256-float chunk: (variable << 1) | mixed
+  uint32_t *bounds = nullptr;  // nvars + 1 running offsets, floats
+  float *mult = nullptr;       // nvars multipliers
+  uint32_t nvars = 0;
+  uint32_t elements = 0;
+};
+struct VarOptArgs {
+  v4f *w, *g, *last, *s;  // as OptArgs; only floats [lo, hi) are read or written
+  uint32_t nvars;         // set by the launcher, as the tables travel beside this block
+  uint32_t lo, hi;        // floats; any values with lo <= hi <= elements
+  uint32_t chunk_lo;      // first chunk of the launch (set by the launcher)
+  uint32_t chunk_hi;      // one past its last chunk
+  float rate;             // -learning rate (sma.cu:43)
+  float momentum;
+  float wd;
+};
+// Updates floats [a.lo, a.hi) only: a float outside the range is never
+// written, not even with its own value (edge chunks use 4-byte stores), so
+// two ranged steps on adjacent variables may run on different streams.  No
+// launch when the range is empty.  The buffers need hold no more than
+// t.elements floats (a last partial chunk is an edge chunk).
+hipError_t launch_sma_optimise_variables(const VarTables &t, VarOptArgs a, const LaunchConfig &cfg,
+                                         hipStream_t stream, Timing tm = {});
+// Uploads host-built tables (optimise_plan.h; blocking) into one device
+// allocation, after freeing what `t` held.  mult == nullptr means all 1.
+hipError_t var_tables_upload(VarTables &t, const uint32_t *chunks, size_t nchunks, const uint32_t *bounds,
+                             const float *mult, uint32_t nvars);
+void var_tables_free(VarTables &t);
 // DEFAULT update model (0, kernels/optimisers/default.cu:3-131): the task
 // step moves the replica and its device's base model by the same gradient.
 // Reads w, g (, last), z; writes g (if changed), last, w, z.

@@ -27,6 +27,7 @@
 // the Phase-D request count through the all-reduce, and -- unless the caller
 // hands over its own (executioncontext.c:185-201) -- the RCCL communicators.
 #include "context_internal.h"
+#include "optimise_plan.h"
 
 using namespace cbx::host;
 
@@ -82,7 +83,9 @@ struct cbx_sma_plan {
     float *bn_scratch = nullptr;
     size_t bn_scratch_bytes = 0;
     cbx::StatsScratch stats;  // cbx_sma_plan_buffer_stats: piece table, slab, results
+    cbx::VarTables var_tables;  // cbx_sma_plan_set_variables: chunk table, bounds, multipliers
   };
+  std::vector<uint32_t> var_bounds;  // cbx_sma_plan_set_variables: nvars + 1 running offsets (empty: not set)
   std::vector<Dev> devs;
   int64_t n = 0;
   int64_t n4b = 0;  // bulk float4s
@@ -300,6 +303,7 @@ int cbx_sma_plan_free(cbx_sma_plan *p) {
     if (d.bn_table) (void)hipFree(d.bn_table);
     if (d.bn_scratch) (void)hipFree(d.bn_scratch);
     cbx::stats_free(d.stats);
+    cbx::var_tables_free(d.var_tables);
     for (hipEvent_t e : d.ev_a) (void)hipEventDestroy(e);
     for (hipEvent_t e : d.ev_r) (void)hipEventDestroy(e);
     if (d.comm_stream) (void)hipStreamDestroy(d.comm_stream);
@@ -770,6 +774,61 @@ int cbx_sma_optimise_buffers(void *stream, float *w, float *g, float *last, floa
   a.tail_lo = a.n4 * 4;  // the elements past the last whole trip ride the same launch
   a.tail_hi = elements;
   HIP_TRY(cbx::launch_sma_optimise(a, cfg, st));
+  return CBX_OK;
+}
+
+int cbx_sma_plan_set_variables(cbx_sma_plan *p, const long long *var_elements, const float *multipliers, int nvars) {
+  TraceRange trace("cbx_sma_plan_set_variables");
+  if (!p) return fail(CBX_ERR_INVALID, "null plan");
+  if (!var_elements || nvars <= 0) return fail(CBX_ERR_INVALID, "cbx_sma_plan_set_variables: no variables");
+  cbx::OptimisePlan plan;
+  if (!cbx::build_optimise_plan(var_elements, nvars, p->n, &plan))
+    return fail(CBX_ERR_INVALID,
+                "cbx_sma_plan_set_variables: %d variables with a negative count, or not summing to the plan's %lld "
+                "elements", nvars, (long long)p->n);
+  for (auto &d : p->devs) {
+    HIP_TRY(hipSetDevice(d.hip_id));
+    HIP_TRY(hipDeviceSynchronize());  // no step in flight still reads the tables being replaced
+    HIP_TRY(cbx::var_tables_upload(d.var_tables, plan.chunks.data(), plan.chunks.size(), plan.bounds.data(),
+                                   multipliers, (uint32_t)nvars));
+  }
+  p->var_bounds = plan.bounds;
+  return CBX_OK;
+}
+
+int cbx_sma_plan_optimise_variables(cbx_sma_plan *p, int k, void *stream, float *w, float *g, float *last, float *s,
+                                    float learning_rate, float momentum, float weight_decay, int first_var,
+                                    int nvars) {
+  TraceRange trace("cbx_sma_plan_optimise_variables");
+  if (!p) return fail(CBX_ERR_INVALID, "null plan");
+  if (k < 0 || k >= (int)p->devs.size()) return fail(CBX_ERR_INVALID, "plan device %d out of range", k);
+  if (p->var_bounds.empty())
+    return fail(CBX_ERR_STATE, "cbx_sma_plan_optimise_variables before cbx_sma_plan_set_variables");
+  const int V = (int)p->var_bounds.size() - 1;
+  if (first_var < 0 || nvars < 0 || first_var > V || nvars > V - first_var)
+    return fail(CBX_ERR_INVALID, "cbx_sma_plan_optimise_variables: variables [%d, %d + %d) out of range [0, %d)",
+                first_var, first_var, nvars, V);
+  if (!w || !g || !s || (momentum > 0.0f && !last))
+    return fail(CBX_ERR_INVALID, "cbx_sma_plan_optimise_variables: missing buffers");
+  if (!aligned16(w) || !aligned16(g) || !aligned16(s) || (momentum > 0.0f && !aligned16(last)))
+    return fail(CBX_ERR_INVALID, "cbx_sma_plan_optimise_variables: buffers must be 16-byte aligned");
+  if (nvars == 0) return CBX_OK;
+  auto &d = p->devs[k];
+  HIP_TRY(hipSetDevice(d.hip_id));
+  cbx::VarOptArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.w = reinterpret_cast<cbx::v4f *>(w);
+  a.g = reinterpret_cast<cbx::v4f *>(g);
+  a.last = momentum > 0.0f ? reinterpret_cast<cbx::v4f *>(last) : nullptr;
+  a.s = reinterpret_cast<cbx::v4f *>(s);
+  a.lo = p->var_bounds[(size_t)first_var];
+  a.hi = p->var_bounds[(size_t)first_var + (size_t)nvars];
+  a.rate = -1.0f * learning_rate;  // sma.cu:43
+  a.momentum = momentum;
+  a.wd = weight_decay;
+  cbx::LaunchConfig cfg = cbx::aux_launch_config();
+  cfg.num_cus = d.num_cus;
+  HIP_TRY(cbx::launch_sma_optimise_variables(d.var_tables, a, cfg, static_cast<hipStream_t>(stream)));
   return CBX_OK;
 }
 

@@ -141,6 +141,28 @@ class SmaPlan:
         o, ov = o[:len(bufs)], ov[:len(bufs)]
         return (r[0], o, rv, ov) if per_variable else (r[0], o)
 
+    def set_variables(self, var_elements: Sequence[int], multipliers: Optional[Sequence[float]] = None) -> None:
+        """``cbx_sma_plan_set_variables``: the variables' float counts in offset
+        order (summing to ``elements``) and their learning-rate multipliers
+        (None: all 1).  Blocks; calling it again replaces the tables."""
+        nv = len(var_elements)
+        ve = (ctypes.c_longlong * max(1, nv))(*var_elements)
+        if multipliers is not None and len(multipliers) != nv:
+            raise ValueError(f"{len(multipliers)} multipliers for {nv} variables")
+        mu = (ctypes.c_float * max(1, nv))(*multipliers) if multipliers is not None else None
+        _raise(self.lib, self.lib.cbx_sma_plan_set_variables(self._p, ve, mu, nv), "cbx_sma_plan_set_variables")
+
+    def optimise_variables(self, k: int, stream: int, w: int, g: int, last: Optional[int], s: int,
+                           learning_rate: float, momentum: float, weight_decay: float, first_var: int,
+                           nvars: int) -> None:
+        """``cbx_sma_plan_optimise_variables``: one task's optimiser step on
+        variables [first_var, first_var + nvars) of buffers on plan device
+        ``k``, each variable with its own rate; asynchronous on ``stream``."""
+        _raise(self.lib, self.lib.cbx_sma_plan_optimise_variables(
+            self._p, k, stream or None, w, g, last or None, s, ctypes.c_float(learning_rate),
+            ctypes.c_float(momentum), ctypes.c_float(weight_decay), first_var, nvars),
+            "cbx_sma_plan_optimise_variables")
+
     def set_buckets(self, buckets: int) -> None:
         """G > 1: buckets of the all-reduce pipeline (0 = default 8, 1 = in order)."""
         _raise(self.lib, self.lib.cbx_sma_plan_set_buckets(self._p, buckets), "cbx_sma_plan_set_buckets")

@@ -118,6 +118,12 @@ class TheGPU:
         SYNCHRONOUSEAMSGD (3) runs elastic averaging instead of SMA."""
         return check(self._L.cbx_set_elastic_average(self._ctx, 1 if enable else 0))
 
+    def set_variable_learning_rates(self, enable: bool) -> int:
+        """``cbx_set_variable_learning_rates``: ``replica_optimise`` steps every
+        variable with its own rate (rate x multiplier, model.c:159-177) under
+        SMA and SYNCHRONOUSEAMSGD, once a multiplier other than 1 is set."""
+        return check(self._L.cbx_set_variable_learning_rates(self._ctx, int(enable)))
+
     # ---- solver (SolverConf.GPURegister, SolverConf.java:355-409) ----------
     def setLearningRateDecayPolicyFixed(self, rate: float) -> int:
         return check(self._L.cbx_set_learning_rate_decay_policy_fixed(self._ctx, rate))
@@ -298,6 +304,13 @@ class TheGPU:
         None enqueues on the replica device's synchronisation stream.
         """
         check(self._L.cbx_replica_optimise(self._ctx, id, task, ctypes.c_void_p(stream) if stream else None))
+
+    def replica_optimise_variables(self, id: int, task: int, op: int, stream: Optional[int] = None) -> None:
+        """crossbowStreamSynchronousEamsgdModelUpdate (stream.c:422-479): the
+        optimiser step of one task on the variables of operator ``op`` only,
+        each with its own learning rate; nothing else is written."""
+        check(self._L.cbx_replica_optimise_variables(self._ctx, id, task, op,
+                                                     ctypes.c_void_p(stream) if stream else None))
 
     def task_wait_count(self, local: int = 0) -> int:
         """Entries in the deferred task-stream wait table of a local device (cbx_task_wait_count; at most 64)."""

@@ -82,9 +82,15 @@ int cbx_set_model_variable (cbx_context *ctx, int id, int order, int ndims,
 		const int *shape, int capacity);
 /* TheGPU.setModelVariableBuffer(IILjava/nio/ByteBuffer;)  GPU.c:698-708 */
 int cbx_set_model_variable_buffer (cbx_context *ctx, int id, int order, const void *src);
-/* TheGPU.setModelVariableLearningRateMultiplier(IIF)  GPU.c:710-719.  Stored
- * (executioncontext.c:1592-1605); the SMA optimiser step ignores it, as the
- * reference's does (optimisers/sma.cu uses the solver rate only).         */
+/* TheGPU.setModelVariableLearningRateMultiplier(IIF)  GPU.c:710-719.  Stored,
+ * and conf.irregular counts every value other than 1
+ * (executioncontext.c:1592-1605).  The replica step honours it where the
+ * reference does (crossbowModelGetLearningRateForVariable, model.c:159-177):
+ * in cbx_replica_optimise once cbx_set_variable_learning_rates is on, and in
+ * cbx_replica_optimise_variables always.  May be called before or after
+ * cbx_set_model_manager.  After it, the call blocks: it waits for every
+ * local device to drain, then copies the one value into the device tables,
+ * so the next step enqueued on any stream uses it.                        */
 int cbx_set_model_variable_learning_rate_multiplier (cbx_context *ctx, int id, int order, float multiplier);
 /* TheGPU.setModelWorkPerClock(I)           GPU.c:721-730  */
 int cbx_set_model_work_per_clock (cbx_context *ctx, int wpc);
@@ -100,6 +106,24 @@ int cbx_set_update_model_type (cbx_context *ctx, int type);
  * May be set before or after cbx_set_model_manager; any other value is
  * CBX_ERR_INVALID.                                                        */
 int cbx_set_elastic_average (cbx_context *ctx, int enable);
+/* Whether cbx_replica_optimise steps every variable with its own learning
+ * rate, rate * multiplier (model.c:165-173), as the reference's optimisers do
+ * when a multiplier other than 1 was registered (conf.irregular > 0,
+ * model.c:167).  0 (the default): one rate for the whole model, whatever
+ * multipliers are set, bit for bit the step as it was.  1: under SMA (7)
+ * and SYNCHRONOUSEAMSGD (3), with elastic averaging on or off, variable v
+ * steps with r_v = -rate * m_v (one fp32 multiply) whenever
+ * conf.irregular > 0; with conf.irregular == 0 the one-rate kernel runs.
+ * WORKER and DEFAULT keep ignoring the multipliers with the switch on.  The
+ * lookup tables are built and uploaded to every local device by
+ * cbx_set_model_manager; replicas added later (cbx_add_model) use them too.
+ * A model whose variables do not tile its elements (a capacity above
+ * 4 x elements) or that was registered as raw bytes has no variable ranges:
+ * with the switch on and conf.irregular > 0 its cbx_replica_optimise is
+ * CBX_ERR_UNSUPPORTED, with a message that names the variable.  May be set
+ * before or after cbx_set_model_manager; any value other than 0 or 1 is
+ * CBX_ERR_INVALID.                                                        */
+int cbx_set_variable_learning_rates (cbx_context *ctx, int enable);
 
 /* ---- solver (SolverConf.GPURegister, SolverConf.java:355-409) --------- */
 /* TheGPU.setLearningRateDecayPolicy*  GPU.c:743-821 */
@@ -348,8 +372,33 @@ int cbx_replica_set_disabled (cbx_context *ctx, int id, int flag);
  * reference's optimisers/synchronouseamsgd.cu is the same call sequence.
  * POLYAK_RUPPERT has no step here (CBX_ERR_UNSUPPORTED): the reference's
  * optimisers/polyakruppert.cu is a stub, so the caller brings its own local
- * step and updates the replica's data itself.                           */
+ * step and updates the replica's data itself.
+ * With cbx_set_variable_learning_rates on (SMA and SYNCHRONOUSEAMSGD only)
+ * and a multiplier other than 1 registered, every variable steps with its
+ * own rate: see there.                                                     */
 int cbx_replica_optimise (cbx_context *ctx, int id, int task, void *stream);
+/* The per-operator step, crossbowStreamSynchronousEamsgdModelUpdate
+ * (stream.c:422-479): cbx_replica_optimise's step on the variables
+ * registered under operator `op` only (orders 1..count), so that the update
+ * of layer k can overlap the backward pass of layer k-1.  It always steps
+ * with the per-variable rate (multipliers apply iff conf.irregular > 0,
+ * model.c:167), whatever cbx_set_variable_learning_rates says.  Floats
+ * outside those variables are not written, not even with their own value,
+ * so steps of different operators may run on different streams.  Variables
+ * that are neighbours in the buffer share one launch, else one launch per
+ * run of neighbours.  g and last keep sma.cu's sign (they hold the
+ * negative-rate values; stream.c:455-467 scales by +rate and subtracts: the
+ * same w, g and last of the opposite sign), so whole-model and per-operator
+ * steps mix on one replica; the snapshot s = w is taken per element here
+ * too.  Everything cbx_replica_optimise does around its launch happens per
+ * call: the learning-rate query (idempotent for a repeated `task`), the
+ * wait for the last barrier, the deferred sync-stream wait, the Nesterov
+ * and missing-`last` refusals.  An operator without variables is CBX_OK
+ * without a launch (stream.c:499-501); `op` out of range is
+ * CBX_ERR_INVALID; WORKER, DEFAULT and POLYAK_RUPPERT are
+ * CBX_ERR_UNSUPPORTED, and so is a model without variable ranges
+ * (cbx_set_variable_learning_rates).                                       */
+int cbx_replica_optimise_variables (cbx_context *ctx, int id, int task, int op, void *stream);
 /* Entries in local device `local`'s table of deferred task-stream waits
  * (see cbx_replica_optimise; at most 64). */
 int cbx_task_wait_count (cbx_context *ctx, int local);
@@ -738,6 +787,26 @@ int cbx_sma_plan_buffer_stats (cbx_sma_plan *plan, int k, void *stream, const fl
  * Nesterov momentum stays the caller's err() (sma.cu:46-48).             */
 int cbx_sma_optimise_buffers (void *stream, float *w, float *g, float *last, float *s, long long elements,
                               float learning_rate, float momentum, float weight_decay);
+/* The same step with a learning rate per variable
+ * (crossbowModelGetLearningRateForVariable, model.c:159-177), whole or on a
+ * range of variables (crossbowStreamSynchronousEamsgdModelUpdate,
+ * stream.c:422-479).  cbx_sma_plan_set_variables attaches the lookup tables
+ * to the plan: var_elements[0..nvars) are the variables' float counts in
+ * offset order and must sum to the plan's `elements`; multipliers[0..nvars)
+ * are v->learningRateMultiplier (NULL: all 1).  It blocks (every plan device
+ * is drained, then the tables are uploaded to it); calling it again replaces
+ * the tables.  cbx_sma_plan_optimise_variables steps variables
+ * [first_var, first_var + nvars) of caller-owned, unpadded, 16-byte-aligned
+ * buffers of `elements` floats on plan device k, asynchronously on `stream`,
+ * with r_v = -learning_rate * multiplier_v (it always multiplies: a caller
+ * without irregular rates keeps calling cbx_sma_optimise_buffers).  Floats
+ * outside the range are not written.  g and last keep sma.cu's sign, as in
+ * cbx_replica_optimise_variables.  nvars == 0 is CBX_OK without a launch.  */
+int cbx_sma_plan_set_variables (cbx_sma_plan *plan, const long long *var_elements, const float *multipliers,
+                                int nvars);
+int cbx_sma_plan_optimise_variables (cbx_sma_plan *plan, int k, void *stream, float *w, float *g, float *last,
+                                     float *s, float learning_rate, float momentum, float weight_decay,
+                                     int first_var, int nvars);
 /* The same seam for update model WORKER (synchronous SGD):
  * crossbowSynchronisationSynchronousSGD (synch/synchronoussgd.c:13-106) ->
  * cbx_ssgd_plan_step, over acc[k] = baseModels[k]->gradient->dev (the
