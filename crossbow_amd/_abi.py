@@ -67,6 +67,17 @@ BUFFER_STATS_FIELDS = [("sum", "<f8"), ("sum_sq", "<f8"), ("dist_sq", "<f8"), ("
                        ("max_abs", "<f4"), ("reserved", "<u4")]
 _BS = _c.POINTER(BufferStats)
 
+
+class ClipStats(_c.Structure):
+    """``cbx_clip_stats``: 48 bytes, no implicit padding."""
+    _fields_ = [("sum_sq", _c.c_double), ("nonfinite", _c.c_ulonglong), ("scale", _c.c_float),
+                ("flags", _c.c_uint), ("steps", _c.c_ulonglong), ("clipped_steps", _c.c_ulonglong),
+                ("skipped_steps", _c.c_ulonglong)]
+
+
+CLIP_CLIPPED, CLIP_SKIPPED = 1, 2  # cbx_clip_stats.flags
+_CS = _c.POINTER(ClipStats)
+
 # name -> (restype, argtypes); mirrors include/crossbow_sma.h one to one.
 SIGNATURES = {
     "cbx_abi_version": (_I, []),
@@ -119,6 +130,8 @@ SIGNATURES = {
     "cbx_replica_learning_rate": (_I, [_P, _I, _I, _FP]),
     "cbx_replica_optimise": (_I, [_P, _I, _I, _P]),
     "cbx_replica_optimise_variables": (_I, [_P, _I, _I, _I, _P]),
+    "cbx_set_gradient_clip": (_I, [_P, _F, _I]),
+    "cbx_replica_clip_stats": (_I, [_P, _I, _CS]),
     "cbx_replica_get_copy": (_I, [_P, _I]),
     "cbx_replica_set_copy": (_I, [_P, _I, _I]),
     "cbx_acquire_access": (_I, [_P, _IP]),
@@ -180,6 +193,9 @@ SIGNATURES = {
     "cbx_sma_optimise_buffers": (_I, [_P, _P, _P, _P, _P, _c.c_longlong, _F, _F, _F]),
     "cbx_sma_plan_set_variables": (_I, [_P, _LLP, _FP, _I]),
     "cbx_sma_plan_optimise_variables": (_I, [_P, _I, _P, _P, _P, _P, _P, _F, _F, _F, _I, _I]),
+    "cbx_sma_plan_optimise_clipped": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _I, _I]),
+    "cbx_sma_plan_clip_stats": (_I, [_P, _I, _I, _P, _CS]),
+    "cbx_sma_plan_gradient_norm": (_I, [_P, _I, _I, _P, _P, _F, _I, _I, _FP, _FP]),
     "cbx_sma_plan_average_batchnorm": (_I, [_P, _I, _IP, _PP, _PP, _IP]),
     "cbx_ssgd_plan_step": (_I, [_P, _PP, _PP, _PP, _PP, _I, _IP, _PP, _IP, _F, _I, _I]),
     "cbx_ssgd_accumulate_buffers": (_I, [_P, _P, _P, _P, _c.c_longlong, _F, _F]),

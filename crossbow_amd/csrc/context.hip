@@ -198,6 +198,12 @@ int cbx_free(cbx_context *c) {
     }
   }
   for (Device &d : c->devs) close_device(d);
+  for (Replica *r : c->replicas) {  // after the streams have drained
+    if (r && r->clip.dev && r->local >= 0) {
+      (void)hipSetDevice(c->devs[r->local].hip_id);
+      cbx::clip_scratch_free(r->clip);
+    }
+  }
   for (std::vector<Replica *> *list : {&c->replicas, &c->retired})
     for (Replica *r : *list) {
       if (!r) continue;
@@ -536,6 +542,7 @@ int cbx_set_model_manager(cbx_context *c, int replicas, int type) {
     for (int id : d.replicas) {
       Replica &r = *c->replicas[id];
       HIP_TRY(hipMemcpyAsync(replica_dev(d, r, CBX_BUF_DATA), z, (size_t)c->n * 4, hipMemcpyDeviceToDevice, d.stream));
+      HIP_TRY(cbx::clip_scratch_alloc(r.clip, c->n));
     }
     HIP_TRY(hipEventRecord(d.synched, d.stream));
     d.step_event = d.synched;
@@ -950,6 +957,7 @@ int cbx_add_model(cbx_context *c) {
       for (int kind : {CBX_BUF_DATA, CBX_BUF_GRADIENT, CBX_BUF_DIFF, CBX_BUF_LAST})
         HIP_TRY(hipMemcpyAsync(replica_dev(d, *r, kind), replica_dev(d, src, kind), d.stride, hipMemcpyDeviceToDevice,
                                d.stream));
+      HIP_TRY(cbx::clip_scratch_alloc(r->clip, c->n));  // a record of its own, all zeros
       HIP_TRY(hipStreamSynchronize(d.stream));
       pthread_mutex_lock(&r->lock);  // :433-435
       c->locked[id] = 1;
@@ -997,6 +1005,7 @@ int cbx_del_model(cbx_context *c) {
       }
       if (r->client) (void)hipEventDestroy(r->client);
       r->client = nullptr;
+      cbx::clip_scratch_free(r->clip);  // every stream has drained above
       d.replicas.erase(std::remove(d.replicas.begin(), d.replicas.end(), id), d.replicas.end());
     }
     pthread_mutex_unlock(&r->lock);
@@ -1139,6 +1148,18 @@ int cbx_set_variable_learning_rates(cbx_context *c, int enable) {
   return CBX_OK;
 }
 
+int cbx_set_gradient_clip(cbx_context *c, float max_norm, int skip_nonfinite) {
+  TRY(check_ctx(c));
+  if (!(max_norm >= 0.0f) || std::isinf(max_norm))
+    return fail(CBX_ERR_INVALID, "cbx_set_gradient_clip: max_norm %g is negative, NaN or infinite", (double)max_norm);
+  if (skip_nonfinite != 0 && skip_nonfinite != 1)
+    return fail(CBX_ERR_INVALID, "cbx_set_gradient_clip: skip_nonfinite %d is neither 0 nor 1", skip_nonfinite);
+  c->clip_max_norm = max_norm;
+  c->clip_skip_nonfinite = skip_nonfinite == 1;
+  c->clip_norm_policy = cbx::clip_norm_policy();
+  return CBX_OK;
+}
+
 // Float ranges [lo, hi) of a replica's buffers.  nullptr: the whole model
 // with the solver's one rate (sma_optimise_kernel); else each range with the
 // rate of its variables (sma_optimise_variables_kernel), one launch each.
@@ -1172,8 +1193,17 @@ static int sma_task_step(cbx_context *c, Replica &r, Device &d, int task, void *
   // The replica must not be updated while the last synchronise() still uses
   // it (the reference's forward kernels wait on replica->updated).
   if (st != d.stream && d.step_event) HIP_TRY(hipStreamWaitEvent(st, d.step_event, 0));
+  const bool clip = c->clip_on();
+  if (clip) {
+    // The whole-model reduction first, on the same stream: S, K, the scale
+    // and the skip bit are in the replica's record when the step reads it.
+    if (!r.clip.dev) return fail(CBX_ERR_STATE, "replica %d has no gradient-clip scratch", r.id);
+    HIP_TRY(cbx::launch_gradient_norm(reinterpret_cast<const float *>(a.g), c->n, r.clip, c->clip_max_norm,
+                                      c->clip_skip_nonfinite, c->clip_norm_policy, st));
+  }
   if (!ranges) {
-    HIP_TRY(cbx::launch_sma_optimise(a, cfg, st, {}));
+    if (clip) HIP_TRY(cbx::launch_sma_optimise_clipped(a, r.clip.record(), cfg, st, {}));
+    else HIP_TRY(cbx::launch_sma_optimise(a, cfg, st, {}));
   } else {
     cbx::VarOptArgs v;
     std::memset(&v, 0, sizeof(v));
@@ -1187,7 +1217,8 @@ static int sma_task_step(cbx_context *c, Replica &r, Device &d, int task, void *
     for (const auto &range : *ranges) {
       v.lo = range.first;
       v.hi = range.second;
-      HIP_TRY(cbx::launch_sma_optimise_variables(d.var_tables, v, cfg, st, {}));
+      if (clip) HIP_TRY(cbx::launch_sma_optimise_variables_clipped(d.var_tables, v, r.clip.record(), cfg, st, {}));
+      else HIP_TRY(cbx::launch_sma_optimise_variables(d.var_tables, v, cfg, st, {}));
     }
   }
   // sma.cu:79-81: the synchronisation stream waits for the updated replica,
@@ -1201,6 +1232,11 @@ static int replica_optimise_impl(cbx_context *c, int id, int task, void *stream)
   Replica &r = *c->replicas[id];
   Device &d = c->devs[r.local];
   const int type = c->model.type;
+  if (c->clip_on() && (type == CBX_UPDATE_WORKER || type == CBX_UPDATE_DEFAULT))
+    return fail(CBX_ERR_UNSUPPORTED,
+                "cbx_replica_optimise with gradient clipping on: update model %d (%s) steps the base model on the sync "
+                "stream and has no clipped step; clipping covers SMA and SYNCHRONOUSEAMSGD",
+                type, type == CBX_UPDATE_WORKER ? "WORKER" : "DEFAULT");
   if (type == CBX_UPDATE_WORKER)
     return ssgd_worker_step(c, r, d, task, stream ? reinterpret_cast<hipStream_t>(stream) : d.stream);
   if (type == CBX_UPDATE_DEFAULT)
@@ -1226,6 +1262,10 @@ static int replica_optimise_variables_impl(cbx_context *c, int id, int task, int
   if (type != CBX_UPDATE_SMA && type != CBX_UPDATE_SYNCHRONOUSEAMSGD)
     return fail(CBX_ERR_UNSUPPORTED, "update model %d has no per-operator optimiser step in this library", type);
   if (op < 0 || op >= c->model.ops) return fail(CBX_ERR_INVALID, "operator %d out of range [0, %d)", op, c->model.ops);
+  if (c->clip_on())
+    return fail(CBX_ERR_UNSUPPORTED,
+                "cbx_replica_optimise_variables with gradient clipping on: the global norm does not exist until every "
+                "operator's gradient does; step the whole model with cbx_replica_optimise");
   if (!c->var_refusal.empty())
     return fail(CBX_ERR_UNSUPPORTED, "cbx_replica_optimise_variables: %s", c->var_refusal.c_str());
   if (c->model.count_per_op[(size_t)op] == 0) return CBX_OK;  // stream.c:499-501
@@ -1650,6 +1690,19 @@ int cbx_replica_read(cbx_context *c, int id, int kind, void *dst, size_t bytes) 
   Device *d = nullptr;
   TRY(replica_ptr(c, id, kind, &p, &d));
   return copy_io(c, d, dst, p, bytes, hipMemcpyDeviceToHost);
+}
+
+int cbx_replica_clip_stats(cbx_context *c, int id, cbx_clip_stats *out) {
+  TRY(check_replica(c, id, true));
+  if (!out) return fail(CBX_ERR_INVALID, "cbx_replica_clip_stats: null result");
+  Replica &r = *c->replicas[id];
+  Device &d = c->devs[r.local];
+  if (!r.clip.dev) return fail(CBX_ERR_STATE, "replica %d has no gradient-clip scratch", id);
+  TRY(flush_task_waits(c));
+  HIP_TRY(hipSetDevice(d.hip_id));
+  HIP_TRY(hipStreamSynchronize(d.stream));
+  HIP_TRY(hipMemcpy(out, r.clip.record(), sizeof(*out), hipMemcpyDeviceToHost));
+  return CBX_OK;
 }
 
 int cbx_base_write(cbx_context *c, int g, int kind, const void *src, size_t bytes) {

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "../../include/crossbow_sma.h"
+#include "clip_internal.h"
 #include "sma_internal.h"
 #include "stats_internal.h"
 
@@ -306,6 +307,10 @@ struct Replica {
   SolverConf conf;
   pthread_mutex_t lock;
   hipEvent_t client = nullptr;  // end of the last optimiser step on a task stream (sma.cu:79)
+  // Gradient clipping (cbx_set_gradient_clip): this replica's record and slab
+  // of partials on its device, allocated with the replica and freed with it.
+  // Per replica, so replicas stepping on different task streams share nothing.
+  cbx::ClipScratch clip;
 };
 
 enum TimingEv { EV_START = 0, EV_A, EV_AR, EV_B, EV_H2D0, EV_H2D1, EV_D2H0, EV_D2H1, EV_COUNT };
@@ -516,6 +521,11 @@ struct cbx_context {
   std::vector<float> var_mult;
   std::vector<std::vector<int>> op_vars;
   std::string var_refusal;
+  // cbx_set_gradient_clip: both zero is off, and the replica step is the plain one.
+  float clip_max_norm = 0.0f;
+  bool clip_skip_nonfinite = false;
+  int clip_norm_policy = cbx::kClipNormPolicy;  // the norm pass's loads of g (clip_internal.h)
+  bool clip_on() const { return clip_max_norm > 0.0f || clip_skip_nonfinite; }
   // BN operators whose running statistics travel with the checkpoint
   // (executioncontext.c:2352-2364): op id -> per-local-device buffers.
   struct BnStats {

@@ -51,6 +51,8 @@ static jint fatal_or (int rc) {
  *   CBX_ENQUEUE_THREADS    -1 | 0 | 1           (cbx_set_enqueue_threads)
  *   CBX_ELASTIC_AVERAGE    0 | 1                (cbx_set_elastic_average)
  *   CBX_VARIABLE_RATES     0 | 1                (cbx_set_variable_learning_rates)
+ *   CBX_GRADIENT_CLIP      max L2 norm, float   (cbx_set_gradient_clip; 0: none)
+ *   CBX_SKIP_NONFINITE_GRADIENTS  0 | 1         (cbx_set_gradient_clip)
  * bench.py's warm-up tuner (crossbow_amd/dist.py) prints the values it
  * chose for a node in its JSON config. */
 static long long env_int (const char *name, int *present) {
@@ -103,6 +105,21 @@ static void configure_from_env (void) {
 	if (on) fatal_or (cbx_set_elastic_average (theGPU, v < 0 || v > 1 ? -1 : (int) v));
 	v = env_int ("CBX_VARIABLE_RATES", &on);
 	if (on) fatal_or (cbx_set_variable_learning_rates (theGPU, v < 0 || v > 1 ? -1 : (int) v));
+	/* gradient clipping: either variable switches it on, the other keeps its default */
+	const char *clip = getenv ("CBX_GRADIENT_CLIP");
+	int have_clip = clip != NULL && *clip != '\0';
+	float max_norm = 0.0f;
+	if (have_clip) {
+		char *end = NULL;
+		max_norm = strtof (clip, &end);
+		if (end == clip || *end != '\0') {
+			fprintf (stderr, "error: CBX_GRADIENT_CLIP=%s is not a number\n", clip);
+			exit (1);
+		}
+	}
+	v = env_int ("CBX_SKIP_NONFINITE_GRADIENTS", &on);
+	if (have_clip || on)
+		fatal_or (cbx_set_gradient_clip (theGPU, max_norm, !on ? 0 : v < 0 || v > 1 ? -1 : (int) v));
 }
 
 /* GPU.c:21-63.  Thread-count / core-offset arguments configure the reference's

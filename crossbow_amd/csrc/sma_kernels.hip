@@ -18,6 +18,7 @@
 // in fp32 and the same operation order, so 1-GPU results equal the oracle's.
 #include <hip/hip_ext.h>
 
+#include "clip_internal.h"
 #include "sma_internal.h"
 #include "stream_helpers.h"
 
@@ -593,8 +594,16 @@ __global__ __launch_bounds__(64) void peer_poison_check_kernel(const uint64_t *b
 //   s = w                                :71 / :87
 //   w = fma(1, g, w)  or  fma(rate, g, w) without momentum  :74 / :90
 // ---------------------------------------------------------------------------
-template <bool MOM, bool WD, int P, bool TAIL, int U>
-__global__ __launch_bounds__(512) void sma_optimise_kernel(const OptArgs a) {
+//
+// CLIP (cbx_set_gradient_clip, clip_kernels.hip): `clip` is the record the
+// norm reduce left on this stream just before.  Its scale and flags are
+// wave-uniform values behind a const __restrict__ kernel parameter, so they
+// come through scalar loads (the scale's behind the trip's float4 loads, the
+// flags' hoisted ahead of the loop by the compiler: DESIGN.md 8e).
+// g = scale * g is one fp32 multiply before weight decay; with the skip bit
+// set only s = w is written.  The other instantiations never touch `clip`.
+template <bool MOM, bool WD, int P, bool TAIL, int U, bool CLIP>
+__global__ __launch_bounds__(512) void sma_optimise_kernel(const OptArgs a, const ClipRecord *__restrict__ clip) {
   if constexpr (TAIL) {
     if (blockIdx.x < (uint32_t)a.tail_blocks) {  // the caller's last elements (see sma_tail_elem)
       const int64_t i = a.tail_lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -602,6 +611,13 @@ __global__ __launch_bounds__(512) void sma_optimise_kernel(const OptArgs a) {
       float *w = reinterpret_cast<float *>(a.w), *g = reinterpret_cast<float *>(a.g);
       const float wv = w[i];
       float gv = g[i];
+      if constexpr (CLIP) {
+        if ((clip->flags & kClipSkipped) != 0u) {
+          reinterpret_cast<float *>(a.s)[i] = wv;
+          return;
+        }
+        gv = clip->scale * gv;
+      }
       if constexpr (WD) gv = fmaf(a.wd, wv, gv);  // sma.cu:24-31
       reinterpret_cast<float *>(a.s)[i] = wv;     // :71 / :87
       if constexpr (MOM) {
@@ -613,7 +629,7 @@ __global__ __launch_bounds__(512) void sma_optimise_kernel(const OptArgs a) {
         g[i] = gv;
       } else {
         w[i] = fmaf(a.rate, gv, wv);  // :90
-        if constexpr (WD) g[i] = gv;
+        if constexpr (WD || CLIP) g[i] = gv;
       }
       return;
     }
@@ -632,6 +648,16 @@ __global__ __launch_bounds__(512) void sma_optimise_kernel(const OptArgs a) {
       if constexpr (MOM) l[u] = ldo<P>(a.last, i);
     }
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (CLIP) {
+      if ((clip->flags & kClipSkipped) != 0u) {  // wave-uniform
+#pragma unroll
+        for (int u = 0; u < U; ++u) sto<P>(a.s, (base + u * 64u) * 16u, w[u]);
+        continue;
+      }
+      const v4f scale = clip->scale;
+#pragma unroll
+      for (int u = 0; u < U; ++u) g[u] = scale * g[u];
+    }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const uint32_t i = (base + u * 64u) * 16u;
@@ -645,7 +671,8 @@ __global__ __launch_bounds__(512) void sma_optimise_kernel(const OptArgs a) {
         sto<P>(a.g, i, g[u]);
       } else {
         sto<P>(a.w, i, vfma(rate, g[u], w[u]));
-        if constexpr (WD) sto<P>(a.g, i, g[u]);
+        // a clipped g is written back as weight decay's is: g holds what was applied
+        if constexpr (WD || CLIP) sto<P>(a.g, i, g[u]);
       }
     }
   }
@@ -1205,40 +1232,53 @@ hipError_t launch_sma_shard_momentum(const SmaArgs &a, const LaunchConfig &cfg0,
       hipExtLaunchKernelGGL((KERNEL<__VA_ARGS__, 1>), g_, dim3(cfg.block), l_, stream, t.start, t.stop, 0, a); \
   } while (0)
 
-template <bool MOM, bool WD, int P>
-hipError_t optimise_p(const OptArgs &a0, const LaunchConfig &cfg, hipStream_t stream, Timing t) {
-  const int reads = 2 + (MOM ? 1 : 0), writes = MOM ? 4 : (WD ? 3 : 2);
+template <bool MOM, bool WD, int P, bool CLIP>
+hipError_t optimise_p(const OptArgs &a0, const ClipRecord *rec, const LaunchConfig &cfg, hipStream_t stream, Timing t) {
+  const int reads = 2 + (MOM ? 1 : 0), writes = MOM ? 4 : ((WD || CLIP) ? 3 : 2);
+  OptArgs a = a0;
+  dim3 g = grid_for(a.n4, cfg);
+  const unsigned l = lds_for_occupancy(cfg, reads, writes, g.x);
   if (a0.tail_hi > a0.tail_lo) {  // caller-owned buffers: the tail rides the same launch
     if constexpr (P != 1) {
       return hipErrorInvalidValue;
     } else {
-      OptArgs a = a0;
-      dim3 g = grid_for(a.n4, cfg);
-      const unsigned l = lds_for_occupancy(cfg, reads, writes, g.x);
       a.tail_blocks = (int)tail_blocks_for(a.tail_lo, a.tail_hi, cfg.block);
       g.x += (unsigned)a.tail_blocks;
       if (cfg.unroll == 2)
-        hipExtLaunchKernelGGL((sma_optimise_kernel<MOM, WD, P, true, 2>), g, dim3(cfg.block), l, stream, t.start, t.stop, 0, a);
+        hipExtLaunchKernelGGL((sma_optimise_kernel<MOM, WD, P, true, 2, CLIP>), g, dim3(cfg.block), l, stream, t.start, t.stop, 0, a, rec);
       else if (cfg.unroll == 1)
-        hipExtLaunchKernelGGL((sma_optimise_kernel<MOM, WD, P, true, 1>), g, dim3(cfg.block), l, stream, t.start, t.stop, 0, a);
+        hipExtLaunchKernelGGL((sma_optimise_kernel<MOM, WD, P, true, 1, CLIP>), g, dim3(cfg.block), l, stream, t.start, t.stop, 0, a, rec);
       else
         return hipErrorInvalidValue;
       return hipGetLastError();
     }
   }
-  const OptArgs &a = a0;
-  CBX_LAUNCH_U(sma_optimise_kernel, MOM, WD, P, false);
+  if (cfg.unroll == 2)
+    hipExtLaunchKernelGGL((sma_optimise_kernel<MOM, WD, P, false, 2, CLIP>), g, dim3(cfg.block), l, stream, t.start, t.stop, 0, a, rec);
+  else
+    hipExtLaunchKernelGGL((sma_optimise_kernel<MOM, WD, P, false, 1, CLIP>), g, dim3(cfg.block), l, stream, t.start, t.stop, 0, a, rec);
   return hipGetLastError();
 }
 
-hipError_t launch_sma_optimise(const OptArgs &a, const LaunchConfig &cfg, hipStream_t stream, Timing t) {
+template <bool CLIP>
+hipError_t optimise_c(const OptArgs &a, const ClipRecord *rec, const LaunchConfig &cfg, hipStream_t stream, Timing t) {
   const bool mom = a.momentum > 0.0f, wd = a.wd > 0.0f;
   if (cfg.policy == 1) {
-    if (mom) return wd ? optimise_p<true, true, 1>(a, cfg, stream, t) : optimise_p<true, false, 1>(a, cfg, stream, t);
-    return wd ? optimise_p<false, true, 1>(a, cfg, stream, t) : optimise_p<false, false, 1>(a, cfg, stream, t);
+    if (mom) return wd ? optimise_p<true, true, 1, CLIP>(a, rec, cfg, stream, t) : optimise_p<true, false, 1, CLIP>(a, rec, cfg, stream, t);
+    return wd ? optimise_p<false, true, 1, CLIP>(a, rec, cfg, stream, t) : optimise_p<false, false, 1, CLIP>(a, rec, cfg, stream, t);
   }
-  if (mom) return wd ? optimise_p<true, true, 0>(a, cfg, stream, t) : optimise_p<true, false, 0>(a, cfg, stream, t);
-  return wd ? optimise_p<false, true, 0>(a, cfg, stream, t) : optimise_p<false, false, 0>(a, cfg, stream, t);
+  if (mom) return wd ? optimise_p<true, true, 0, CLIP>(a, rec, cfg, stream, t) : optimise_p<true, false, 0, CLIP>(a, rec, cfg, stream, t);
+  return wd ? optimise_p<false, true, 0, CLIP>(a, rec, cfg, stream, t) : optimise_p<false, false, 0, CLIP>(a, rec, cfg, stream, t);
+}
+
+hipError_t launch_sma_optimise(const OptArgs &a, const LaunchConfig &cfg, hipStream_t stream, Timing t) {
+  return optimise_c<false>(a, nullptr, cfg, stream, t);
+}
+
+hipError_t launch_sma_optimise_clipped(const OptArgs &a, const ClipRecord *rec, const LaunchConfig &cfg,
+                                       hipStream_t stream, Timing t) {
+  if (!rec) return hipErrorInvalidValue;
+  return optimise_c<true>(a, rec, cfg, stream, t);
 }
 
 template <bool MOM, bool WD, int P>

@@ -64,6 +64,7 @@ int64_t bulk_float4s(int64_t n) { return (n / 4) / kTailQuantum4 * kTailQuantum4
 }  // namespace
 
 struct cbx_sma_plan {
+  static constexpr int kClipSlots = 64;
   struct Dev {
     int hip_id = 0;
     int num_cus = 256;
@@ -84,7 +85,12 @@ struct cbx_sma_plan {
     size_t bn_scratch_bytes = 0;
     cbx::StatsScratch stats;  // cbx_sma_plan_buffer_stats: piece table, slab, results
     cbx::VarTables var_tables;  // cbx_sma_plan_set_variables: chunk table, bounds, multipliers
+    // cbx_sma_plan_optimise_clipped: record and slab per slot, allocated on a
+    // slot's first use (clip_mu held).
+    cbx::ClipScratch clip[kClipSlots];
   };
+  std::mutex clip_mu;
+  int clip_norm_policy = cbx::clip_norm_policy();
   std::vector<uint32_t> var_bounds;  // cbx_sma_plan_set_variables: nvars + 1 running offsets (empty: not set)
   std::vector<Dev> devs;
   int64_t n = 0;
@@ -304,6 +310,7 @@ int cbx_sma_plan_free(cbx_sma_plan *p) {
     if (d.bn_scratch) (void)hipFree(d.bn_scratch);
     cbx::stats_free(d.stats);
     cbx::var_tables_free(d.var_tables);
+    for (cbx::ClipScratch &cs : d.clip) cbx::clip_scratch_free(cs);
     for (hipEvent_t e : d.ev_a) (void)hipEventDestroy(e);
     for (hipEvent_t e : d.ev_r) (void)hipEventDestroy(e);
     if (d.comm_stream) (void)hipStreamDestroy(d.comm_stream);
@@ -829,6 +836,123 @@ int cbx_sma_plan_optimise_variables(cbx_sma_plan *p, int k, void *stream, float 
   cbx::LaunchConfig cfg = cbx::aux_launch_config();
   cfg.num_cus = d.num_cus;
   HIP_TRY(cbx::launch_sma_optimise_variables(d.var_tables, a, cfg, static_cast<hipStream_t>(stream)));
+  return CBX_OK;
+}
+
+namespace {
+
+// The slot's scratch on plan device k (the current device), allocated and
+// zeroed on first use.
+int clip_slot(cbx_sma_plan *p, const char *what, int k, int slot, cbx::ClipScratch **out) {
+  if (!p) return fail(CBX_ERR_INVALID, "null plan");
+  if (k < 0 || k >= (int)p->devs.size()) return fail(CBX_ERR_INVALID, "plan device %d out of range", k);
+  if (slot < 0 || slot >= cbx_sma_plan::kClipSlots)
+    return fail(CBX_ERR_INVALID, "%s: slot %d out of range [0, %d)", what, slot, cbx_sma_plan::kClipSlots);
+  auto &d = p->devs[k];
+  HIP_TRY(hipSetDevice(d.hip_id));
+  std::lock_guard<std::mutex> lock(p->clip_mu);
+  if (!d.clip[slot].dev) HIP_TRY(cbx::clip_scratch_alloc(d.clip[slot], p->n));
+  *out = &d.clip[slot];
+  return CBX_OK;
+}
+
+}  // namespace
+
+int cbx_sma_plan_optimise_clipped(cbx_sma_plan *p, int k, int slot, void *stream, float *w, float *g, float *last,
+                                  float *s, float learning_rate, float momentum, float weight_decay, float max_norm,
+                                  int skip_nonfinite, int use_variables) {
+  TraceRange trace("cbx_sma_plan_optimise_clipped");
+  if (!p) return fail(CBX_ERR_INVALID, "null plan");
+  if (!(max_norm >= 0.0f) || std::isinf(max_norm))
+    return fail(CBX_ERR_INVALID, "cbx_sma_plan_optimise_clipped: max_norm %g is negative, NaN or infinite",
+                (double)max_norm);
+  if (skip_nonfinite != 0 && skip_nonfinite != 1)
+    return fail(CBX_ERR_INVALID, "cbx_sma_plan_optimise_clipped: skip_nonfinite %d is neither 0 nor 1", skip_nonfinite);
+  if (use_variables != 0 && use_variables != 1)
+    return fail(CBX_ERR_INVALID, "cbx_sma_plan_optimise_clipped: use_variables %d is neither 0 nor 1", use_variables);
+  if (use_variables && p->var_bounds.empty())
+    return fail(CBX_ERR_STATE, "cbx_sma_plan_optimise_clipped with variables before cbx_sma_plan_set_variables");
+  if (!w || !g || !s || (momentum > 0.0f && !last))
+    return fail(CBX_ERR_INVALID, "cbx_sma_plan_optimise_clipped: missing buffers");
+  if (!aligned16(w) || !aligned16(g) || !aligned16(s) || (momentum > 0.0f && !aligned16(last)))
+    return fail(CBX_ERR_INVALID, "cbx_sma_plan_optimise_clipped: buffers must be 16-byte aligned");
+  cbx::ClipScratch *cs = nullptr;
+  TRY(clip_slot(p, "cbx_sma_plan_optimise_clipped", k, slot, &cs));
+  auto &d = p->devs[k];
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  cbx::LaunchConfig cfg = cbx::aux_launch_config();
+  cfg.num_cus = d.num_cus;
+  HIP_TRY(cbx::launch_gradient_norm(g, p->n, *cs, max_norm, skip_nonfinite == 1, p->clip_norm_policy, st));
+  if (use_variables) {
+    cbx::VarOptArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.w = reinterpret_cast<cbx::v4f *>(w);
+    a.g = reinterpret_cast<cbx::v4f *>(g);
+    a.last = momentum > 0.0f ? reinterpret_cast<cbx::v4f *>(last) : nullptr;
+    a.s = reinterpret_cast<cbx::v4f *>(s);
+    a.lo = 0;
+    a.hi = p->var_bounds.back();
+    a.rate = -1.0f * learning_rate;  // sma.cu:43
+    a.momentum = momentum;
+    a.wd = weight_decay;
+    HIP_TRY(cbx::launch_sma_optimise_variables_clipped(d.var_tables, a, cs->record(), cfg, st));
+    return CBX_OK;
+  }
+  cbx::OptArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.w = reinterpret_cast<cbx::v4f *>(w);
+  a.g = reinterpret_cast<cbx::v4f *>(g);
+  a.last = momentum > 0.0f ? reinterpret_cast<cbx::v4f *>(last) : nullptr;
+  a.s = reinterpret_cast<cbx::v4f *>(s);
+  a.n4 = p->n4b;
+  a.rate = -1.0f * learning_rate;  // sma.cu:43
+  a.momentum = momentum;
+  a.wd = weight_decay;
+  a.tail_lo = a.n4 * 4;  // the elements past the last whole trip ride the same launch
+  a.tail_hi = p->n;
+  HIP_TRY(cbx::launch_sma_optimise_clipped(a, cs->record(), cfg, st));
+  return CBX_OK;
+}
+
+int cbx_sma_plan_gradient_norm(cbx_sma_plan *p, int k, int slot, void *stream, const float *g, float max_norm,
+                               int skip_nonfinite, int loads, float *pass_ms, float *reduce_ms) {
+  TraceRange trace("cbx_sma_plan_gradient_norm");
+  if (!p) return fail(CBX_ERR_INVALID, "null plan");
+  if (!(max_norm >= 0.0f) || std::isinf(max_norm) || (skip_nonfinite != 0 && skip_nonfinite != 1) || loads < -1 ||
+      loads > 1)
+    return fail(CBX_ERR_INVALID, "cbx_sma_plan_gradient_norm: max_norm %g, skip_nonfinite %d or loads %d out of range",
+                (double)max_norm, skip_nonfinite, loads);
+  if (!g || !aligned16(g)) return fail(CBX_ERR_INVALID, "cbx_sma_plan_gradient_norm: g must be non-null and 16-byte aligned");
+  cbx::ClipScratch *cs = nullptr;
+  TRY(clip_slot(p, "cbx_sma_plan_gradient_norm", k, slot, &cs));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  const bool timed = pass_ms || reduce_ms;
+  int rc = CBX_OK;
+  auto run = [&]() -> int {
+    if (timed)
+      for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(cbx::launch_gradient_norm(g, p->n, *cs, max_norm, skip_nonfinite == 1,
+                                      loads < 0 ? p->clip_norm_policy : loads, st, {ev[0], ev[1]}, {ev[2], ev[3]}));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (pass_ms) HIP_TRY(hipEventElapsedTime(pass_ms, ev[0], ev[1]));
+    if (reduce_ms) HIP_TRY(hipEventElapsedTime(reduce_ms, ev[2], ev[3]));
+    return CBX_OK;
+  };
+  rc = run();
+  for (hipEvent_t e : ev)
+    if (e) (void)hipEventDestroy(e);
+  return rc;
+}
+
+int cbx_sma_plan_clip_stats(cbx_sma_plan *p, int k, int slot, void *stream, cbx_clip_stats *out) {
+  TraceRange trace("cbx_sma_plan_clip_stats");
+  if (!out) return fail(CBX_ERR_INVALID, "cbx_sma_plan_clip_stats: null result");
+  cbx::ClipScratch *cs = nullptr;
+  TRY(clip_slot(p, "cbx_sma_plan_clip_stats", k, slot, &cs));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  HIP_TRY(hipMemcpyAsync(out, cs->record(), sizeof(*out), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   return CBX_OK;
 }
 

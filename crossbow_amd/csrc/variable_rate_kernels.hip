@@ -35,6 +35,7 @@
 #include <cstring>
 #include <vector>
 
+#include "clip_internal.h"
 #include "optimise_plan.h"
 #include "sma_internal.h"
 #include "stream_helpers.h"
@@ -55,11 +56,14 @@ __device__ __forceinline__ uint32_t variable_of(const uint32_t *__restrict__ bou
   return lo;
 }
 
-template <bool MOM, bool WD, int P, int U>
+// CLIP: as sma_optimise_kernel's (sma_kernels.hip): g = scale * g before weight
+// decay on all three paths, s = w alone when the record carries the skip bit.
+template <bool MOM, bool WD, int P, int U, bool CLIP>
 __global__ __launch_bounds__(512) void sma_optimise_variables_kernel(const VarOptArgs a,
                                                                            const uint32_t *__restrict__ chunks,
                                                                            const uint32_t *__restrict__ bounds,
-                                                                           const float *__restrict__ mult) {
+                                                                           const float *__restrict__ mult,
+                                                                           const ClipRecord *__restrict__ clip) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t waves = gridDim.x * (blockDim.x >> 6);
   const uint32_t wave =
@@ -80,6 +84,16 @@ __global__ __launch_bounds__(512) void sma_optimise_variables_kernel(const VarOp
         if constexpr (MOM) l[u] = ldo<P>(a.last, i);
       }
       __builtin_amdgcn_sched_barrier(0);
+      if constexpr (CLIP) {
+        if ((clip->flags & kClipSkipped) != 0u) {  // wave-uniform
+#pragma unroll
+          for (int u = 0; u < U; ++u) sto<P>(a.s, ((c + u) * 64u + lane) * 16u, w[u]);
+          continue;
+        }
+        const v4f scale = clip->scale;
+#pragma unroll
+        for (int u = 0; u < U; ++u) g[u] = scale * g[u];
+      }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const uint32_t v0 = e[u] >> 1;
@@ -104,7 +118,7 @@ __global__ __launch_bounds__(512) void sma_optimise_variables_kernel(const VarOp
           sto<P>(a.g, i, g[u]);
         } else {
           sto<P>(a.w, i, vfma(r[u], g[u], w[u]));
-          if constexpr (WD) sto<P>(a.g, i, g[u]);
+          if constexpr (WD || CLIP) sto<P>(a.g, i, g[u]);
         }
       }
     } else {
@@ -122,6 +136,13 @@ __global__ __launch_bounds__(512) void sma_optimise_variables_kernel(const VarOp
           const float rv = a.rate * mult[v];
           const float wv = wp[f];
           float gv = gp[f];
+          if constexpr (CLIP) {
+            if ((clip->flags & kClipSkipped) != 0u) {
+              sp[f] = wv;
+              continue;
+            }
+            gv = clip->scale * gv;
+          }
           if constexpr (WD) gv = fmaf(a.wd, wv, gv);
           sp[f] = wv;
           if constexpr (MOM) {
@@ -132,7 +153,7 @@ __global__ __launch_bounds__(512) void sma_optimise_variables_kernel(const VarOp
             gp[f] = gv;
           } else {
             wp[f] = fmaf(rv, gv, wv);
-            if constexpr (WD) gp[f] = gv;
+            if constexpr (WD || CLIP) gp[f] = gv;
           }
         }
       }
@@ -140,28 +161,27 @@ __global__ __launch_bounds__(512) void sma_optimise_variables_kernel(const VarOp
   }
 }
 
-template <bool MOM, bool WD, int P>
-hipError_t variables_p(const VarTables &vt, const VarOptArgs &a, const LaunchConfig &cfg, hipStream_t stream,
-                       Timing t) {
-  const int reads = 2 + (MOM ? 1 : 0), writes = MOM ? 4 : (WD ? 3 : 2);
+template <bool MOM, bool WD, int P, bool CLIP>
+hipError_t variables_p(const VarTables &vt, const VarOptArgs &a, const ClipRecord *rec, const LaunchConfig &cfg,
+                       hipStream_t stream, Timing t) {
+  const int reads = 2 + (MOM ? 1 : 0), writes = MOM ? 4 : ((WD || CLIP) ? 3 : 2);
   const int64_t n4 = (int64_t)(a.chunk_hi - a.chunk_lo) * 64;
   const dim3 g = grid_for(n4, cfg);
   const unsigned l = lds_for_occupancy(cfg, reads, writes, g.x);
   if (cfg.unroll == 2)
-    hipExtLaunchKernelGGL((sma_optimise_variables_kernel<MOM, WD, P, 2>), g, dim3(cfg.block), l, stream, t.start,
-                          t.stop, 0, a, vt.chunks, vt.bounds, vt.mult);
+    hipExtLaunchKernelGGL((sma_optimise_variables_kernel<MOM, WD, P, 2, CLIP>), g, dim3(cfg.block), l, stream,
+                          t.start, t.stop, 0, a, vt.chunks, vt.bounds, vt.mult, rec);
   else if (cfg.unroll == 1)
-    hipExtLaunchKernelGGL((sma_optimise_variables_kernel<MOM, WD, P, 1>), g, dim3(cfg.block), l, stream, t.start,
-                          t.stop, 0, a, vt.chunks, vt.bounds, vt.mult);
+    hipExtLaunchKernelGGL((sma_optimise_variables_kernel<MOM, WD, P, 1, CLIP>), g, dim3(cfg.block), l, stream,
+                          t.start, t.stop, 0, a, vt.chunks, vt.bounds, vt.mult, rec);
   else
     return hipErrorInvalidValue;
   return hipGetLastError();
 }
 
-}  // namespace
-
-hipError_t launch_sma_optimise_variables(const VarTables &t, VarOptArgs a, const LaunchConfig &cfg,
-                                         hipStream_t stream, Timing tm) {
+template <bool CLIP>
+hipError_t variables_c(const VarTables &t, VarOptArgs a, const ClipRecord *rec, const LaunchConfig &cfg,
+                       hipStream_t stream, Timing tm) {
   if (!t.chunks || a.lo > a.hi || a.hi > t.elements || cfg.block < 64 || cfg.block % 64 != 0 || cfg.block > 512)
     return hipErrorInvalidValue;
   if (a.lo == a.hi) return hipSuccess;
@@ -170,11 +190,30 @@ hipError_t launch_sma_optimise_variables(const VarTables &t, VarOptArgs a, const
   a.chunk_hi = (a.hi + kOptChunk - 1) / kOptChunk;
   const bool mom = a.momentum > 0.0f, wd = a.wd > 0.0f;
   if (cfg.policy == 1) {
-    if (mom) return wd ? variables_p<true, true, 1>(t, a, cfg, stream, tm) : variables_p<true, false, 1>(t, a, cfg, stream, tm);
-    return wd ? variables_p<false, true, 1>(t, a, cfg, stream, tm) : variables_p<false, false, 1>(t, a, cfg, stream, tm);
+    if (mom)
+      return wd ? variables_p<true, true, 1, CLIP>(t, a, rec, cfg, stream, tm)
+                : variables_p<true, false, 1, CLIP>(t, a, rec, cfg, stream, tm);
+    return wd ? variables_p<false, true, 1, CLIP>(t, a, rec, cfg, stream, tm)
+              : variables_p<false, false, 1, CLIP>(t, a, rec, cfg, stream, tm);
   }
-  if (mom) return wd ? variables_p<true, true, 0>(t, a, cfg, stream, tm) : variables_p<true, false, 0>(t, a, cfg, stream, tm);
-  return wd ? variables_p<false, true, 0>(t, a, cfg, stream, tm) : variables_p<false, false, 0>(t, a, cfg, stream, tm);
+  if (mom)
+    return wd ? variables_p<true, true, 0, CLIP>(t, a, rec, cfg, stream, tm)
+              : variables_p<true, false, 0, CLIP>(t, a, rec, cfg, stream, tm);
+  return wd ? variables_p<false, true, 0, CLIP>(t, a, rec, cfg, stream, tm)
+            : variables_p<false, false, 0, CLIP>(t, a, rec, cfg, stream, tm);
+}
+
+}  // namespace
+
+hipError_t launch_sma_optimise_variables(const VarTables &t, VarOptArgs a, const LaunchConfig &cfg,
+                                         hipStream_t stream, Timing tm) {
+  return variables_c<false>(t, a, nullptr, cfg, stream, tm);
+}
+
+hipError_t launch_sma_optimise_variables_clipped(const VarTables &t, VarOptArgs a, const ClipRecord *rec,
+                                                 const LaunchConfig &cfg, hipStream_t stream, Timing tm) {
+  if (!rec) return hipErrorInvalidValue;
+  return variables_c<true>(t, a, rec, cfg, stream, tm);
 }
 
 hipError_t var_tables_upload(VarTables &t, const uint32_t *chunks, size_t nchunks, const uint32_t *bounds,

@@ -163,6 +163,37 @@ class SmaPlan:
             ctypes.c_float(momentum), ctypes.c_float(weight_decay), first_var, nvars),
             "cbx_sma_plan_optimise_variables")
 
+    def optimise_clipped(self, k: int, slot: int, stream: int, w: int, g: int, last: Optional[int], s: int,
+                         learning_rate: float, momentum: float, weight_decay: float, max_norm: float,
+                         skip_nonfinite: bool = False, use_variables: bool = False) -> None:
+        """``cbx_sma_plan_optimise_clipped``: one task's optimiser step with
+        gradient clipping by global L2 norm (``max_norm``; 0: none) and the
+        non-finite skip, on plan device ``k``; asynchronous on ``stream``.
+        ``slot`` in [0, 64) names the plan-owned record and slab."""
+        _raise(self.lib, self.lib.cbx_sma_plan_optimise_clipped(
+            self._p, k, slot, stream or None, w, g, last or None, s, ctypes.c_float(learning_rate),
+            ctypes.c_float(momentum), ctypes.c_float(weight_decay), ctypes.c_float(max_norm),
+            1 if skip_nonfinite else 0, 1 if use_variables else 0), "cbx_sma_plan_optimise_clipped")
+
+    def gradient_norm(self, k: int, slot: int, stream: int, g: int, max_norm: float = 0.0,
+                      skip_nonfinite: bool = False, loads: int = -1):
+        """``cbx_sma_plan_gradient_norm``: the norm pass and the reduce alone
+        over ``g`` (blocking).  Returns (the slot's record, pass ms, reduce
+        ms), the times from the two dispatches' own timestamps."""
+        a, b = ctypes.c_float(-1), ctypes.c_float(-1)
+        _raise(self.lib, self.lib.cbx_sma_plan_gradient_norm(
+            self._p, k, slot, stream or None, g, ctypes.c_float(max_norm), 1 if skip_nonfinite else 0, loads,
+            ctypes.byref(a), ctypes.byref(b)), "cbx_sma_plan_gradient_norm")
+        return self.clip_stats(k, slot, stream), a.value, b.value
+
+    def clip_stats(self, k: int, slot: int, stream: int) -> dict:
+        """``cbx_sma_plan_clip_stats``: the slot's record (blocks on
+        ``stream``), as a dict of the fields of ``cbx_clip_stats``."""
+        out = self.lib.cbx_sma_plan_clip_stats.argtypes[4]._type_()
+        _raise(self.lib, self.lib.cbx_sma_plan_clip_stats(self._p, k, slot, stream or None, ctypes.byref(out)),
+               "cbx_sma_plan_clip_stats")
+        return {name: getattr(out, name) for name, _ in out._fields_}
+
     def set_buckets(self, buckets: int) -> None:
         """G > 1: buckets of the all-reduce pipeline (0 = default 8, 1 = in order)."""
         _raise(self.lib, self.lib.cbx_sma_plan_set_buckets(self._p, buckets), "cbx_sma_plan_set_buckets")

@@ -124,6 +124,20 @@ class TheGPU:
         SMA and SYNCHRONOUSEAMSGD, once a multiplier other than 1 is set."""
         return check(self._L.cbx_set_variable_learning_rates(self._ctx, int(enable)))
 
+    def set_gradient_clip(self, max_norm: float, skip_nonfinite: bool = False) -> int:
+        """``cbx_set_gradient_clip``: ``replica_optimise`` clips the replica's
+        gradient to a global L2 norm of ``max_norm`` (0: no clipping) and, with
+        ``skip_nonfinite``, leaves w, g and last alone when the gradient holds
+        a NaN or an infinity (s = w is still written).  Both zero: off."""
+        return check(self._L.cbx_set_gradient_clip(self._ctx, ctypes.c_float(max_norm), int(skip_nonfinite)))
+
+    def replica_clip_stats(self, id: int) -> dict:
+        """``cbx_replica_clip_stats`` (blocking): the replica's record as a
+        dict of the fields of ``cbx_clip_stats``."""
+        out = _lib.ClipStats()
+        check(self._L.cbx_replica_clip_stats(self._ctx, id, ctypes.byref(out)))
+        return {name: getattr(out, name) for name, _ in out._fields_}
+
     # ---- solver (SolverConf.GPURegister, SolverConf.java:355-409) ----------
     def setLearningRateDecayPolicyFixed(self, rate: float) -> int:
         return check(self._L.cbx_set_learning_rate_decay_policy_fixed(self._ctx, rate))

@@ -399,6 +399,62 @@ int cbx_replica_optimise (cbx_context *ctx, int id, int task, void *stream);
  * CBX_ERR_UNSUPPORTED, and so is a model without variable ranges
  * (cbx_set_variable_learning_rates).                                       */
 int cbx_replica_optimise_variables (cbx_context *ctx, int id, int task, int op, void *stream);
+
+/* ---- gradient clipping by global norm, non-finite skip ----------------- */
+/* An extension: the reference has no gradient clipping.  Opt-in, off by
+ * default; off, cbx_replica_optimise is exactly the step above (no extra
+ * launch, the same kernels).  On, every cbx_replica_optimise under SMA (7) or
+ * SYNCHRONOUSEAMSGD (3), one rate or per-variable rates, first reduces the
+ * replica's gradient on the device, on the caller's stream, with no host
+ * round trip (crossbow_amd/csrc/clip_kernels.hip).  Per call, with
+ * c = max_norm and g the replica's gradient as the backward pass left it,
+ * over exactly the model's n floats (a buffer's pad is never read):
+ *   1. S = sum of (double)g_i * (double)g_i over finite g_i, accumulated in
+ *      fp64 from the first add in an order that is a fixed function of n
+ *      alone (never of the CU count, cbx_set_aux_kernel_config or the
+ *      stream); K = the count of non-finite g_i.
+ *   2. clipped = c > 0 && S > (double)c * (double)c (the product is exact,
+ *      the decision takes no square root);
+ *      scale = clipped ? (float)((double)c / sqrt (S)) : 1.0f.
+ *   3. skipped = skip_nonfinite && K > 0.
+ *   4. Not skipped: g_i = scale * g_i, one fp32 multiply before weight decay
+ *      (clipping acts on the raw gradient), then the step's sequence
+ *      unchanged; g is written back.  With scale == 1.0f the result is bit
+ *      for bit the plain step's.  A non-finite g_i with skip_nonfinite == 0
+ *      propagates exactly as it does in the plain step.
+ *   5. Skipped: s = w is still written (the snapshot says "no local
+ *      movement", what the next barrier's d = s - z must see); w, g and last
+ *      are not written at all.
+ *   6. The replica's record on the device is updated: the last S, K, scale,
+ *      flags, and running counts (a step both clipped and skipped counts in
+ *      both).  Steps of one replica are ordered by the caller, as for w and g.
+ * The host side of the step (learning-rate query, _copy, the Nesterov and
+ * missing-`last` refusals, the deferred sync-stream wait) happens exactly as
+ * in the plain step, also for a skipped one.
+ * max_norm == 0: no clipping; both arguments 0: off.  A negative, NaN or
+ * infinite max_norm, or a flag other than 0 / 1, is CBX_ERR_INVALID.  May be
+ * called before or after cbx_set_model_manager.  While the feature is on,
+ * cbx_replica_optimise_variables is CBX_ERR_UNSUPPORTED (the global norm does
+ * not exist until every operator's gradient does), and so is
+ * cbx_replica_optimise under WORKER and DEFAULT.  With several devices per
+ * context every local device's replicas carry their own record and slab; that
+ * path has not run on several devices.                                      */
+int cbx_set_gradient_clip (cbx_context *ctx, float max_norm, int skip_nonfinite);
+#define CBX_CLIP_CLIPPED 1u     /* cbx_clip_stats.flags: the last step was scaled   */
+#define CBX_CLIP_SKIPPED 2u     /*                       the last step was skipped  */
+typedef struct cbx_clip_stats {
+  double sum_sq;                    /* S of the last step                            */
+  unsigned long long nonfinite;     /* K of the last step                            */
+  float  scale;                     /* the last step's scale (1 when not clipped)    */
+  unsigned int flags;               /* CBX_CLIP_CLIPPED | CBX_CLIP_SKIPPED           */
+  unsigned long long steps;         /* steps taken with the feature on               */
+  unsigned long long clipped_steps; /* of those, clipped                             */
+  unsigned long long skipped_steps; /* of those, skipped                             */
+} cbx_clip_stats;                   /* 48 bytes, no implicit padding                 */
+/* Blocking: drains as cbx_replica_read does, then copies replica `id`'s
+ * record back.  All zeros before the replica's first step with the feature
+ * on.                                                                       */
+int cbx_replica_clip_stats (cbx_context *ctx, int id, cbx_clip_stats *out);
 /* Entries in local device `local`'s table of deferred task-stream waits
  * (see cbx_replica_optimise; at most 64). */
 int cbx_task_wait_count (cbx_context *ctx, int local);
@@ -807,6 +863,32 @@ int cbx_sma_plan_set_variables (cbx_sma_plan *plan, const long long *var_element
 int cbx_sma_plan_optimise_variables (cbx_sma_plan *plan, int k, void *stream, float *w, float *g, float *last,
                                      float *s, float learning_rate, float momentum, float weight_decay,
                                      int first_var, int nvars);
+/* The step with gradient clipping by global norm and the non-finite skip
+ * (cbx_set_gradient_clip: the same semantics, kernels and bits of S on the
+ * same data), over caller-owned, unpadded, 16-byte-aligned buffers of the
+ * plan's `elements` floats on plan device k, asynchronously on `stream`:
+ * norm pass, reduce and step.  `slot` in [0, 64) names plan-owned scratch
+ * (record and slab, allocated on the slot's first use), so 64 replicas can be
+ * in flight; steps that share a slot are ordered by the caller.
+ * use_variables == 1 (needs cbx_sma_plan_set_variables): the per-variable
+ * step over every variable; 0: cbx_sma_optimise_buffers' step.  max_norm and
+ * skip_nonfinite as in cbx_set_gradient_clip, both 0 included (the reduction
+ * still runs and the record counts the step).  cbx_sma_plan_clip_stats
+ * blocks on `stream`, then copies the slot's record back: all zeros before
+ * the slot's first step.                                                   */
+int cbx_sma_plan_optimise_clipped (cbx_sma_plan *plan, int k, int slot, void *stream, float *w, float *g,
+                                   float *last, float *s, float learning_rate, float momentum, float weight_decay,
+                                   float max_norm, int skip_nonfinite, int use_variables);
+int cbx_sma_plan_clip_stats (cbx_sma_plan *plan, int k, int slot, void *stream, cbx_clip_stats *out);
+/* The reduction alone (norm pass and reduce, no step) over g on plan device k,
+ * blocking on `stream`: a caller's look at its gradient's norm, and the
+ * measurement of the two launches.  The slot's record is updated as a step's
+ * reduction updates it (it counts a step).  loads: 0 plain, 1 nontemporal
+ * loads of g, -1 the library's choice.  pass_ms / reduce_ms (either may be
+ * NULL): device milliseconds of the two dispatches, from their own
+ * timestamps.                                                              */
+int cbx_sma_plan_gradient_norm (cbx_sma_plan *plan, int k, int slot, void *stream, const float *g, float max_norm,
+                                int skip_nonfinite, int loads, float *pass_ms, float *reduce_ms);
 /* The same seam for update model WORKER (synchronous SGD):
  * crossbowSynchronisationSynchronousSGD (synch/synchronoussgd.c:13-106) ->
  * cbx_ssgd_plan_step, over acc[k] = baseModels[k]->gradient->dev (the
