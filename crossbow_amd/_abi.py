@@ -33,6 +33,7 @@ UPDATE_DEFAULT, UPDATE_WORKER, UPDATE_SYNCHRONOUSEAMSGD, UPDATE_POLYAK_RUPPERT, 
 ALLREDUCE_RCCL, ALLREDUCE_PEER, ALLREDUCE_RSAG = 0, 1, 2
 PEER_BLOB_BYTES = 256  # CBX_PEER_BLOB_BYTES
 STAGING_ZEROCOPY, STAGING_DMA = 0, 1
+STEP_DISCARD_TASK_OUTPUTS = 1  # CBX_STEP_DISCARD_TASK_OUTPUTS
 
 
 class CbxError(RuntimeError):
@@ -111,6 +112,7 @@ SIGNATURES = {
     "cbx_merge": (_I, [_P, _I, _IP]),
     "cbx_synchronise": (_I, [_P, _I, _I, _I, _I]),
     "cbx_synchronise_staged": (_I, [_P, _I, _I, _I, _I]),
+    "cbx_step_and_synchronise": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
     "cbx_unlock_any": (_I, [_P]),
     "cbx_checkpoint_model": (_I, [_P, _CP]),
     "cbx_override_model_data": (_I, [_P, _CP]),
@@ -168,6 +170,7 @@ SIGNATURES = {
     "cbx_set_barrier_kernel_config": (_I, [_P, _I, _I, _I]),
     "cbx_set_apply_kernel_config": (_I, [_P, _I, _I, _I]),
     "cbx_set_averaging_kernel_config": (_I, [_P, _I, _I, _I]),
+    "cbx_set_task_barrier_kernel_config": (_I, [_P, _I, _I, _I]),
     "cbx_set_pipeline_mode": (_I, [_P, _I]),
     "cbx_set_cross_wait_stride": (_I, [_P, _I]),
     "cbx_set_allreduce_group": (_I, [_P, _I]),

@@ -3,7 +3,8 @@
 * ``crossbow_amd/libcrossbow_sma.so``  -- the C-ABI library (hipcc, gfx950):
   csrc/context.hip + csrc/sync_steps.hip + csrc/sma_kernels.hip +
   csrc/averaging_kernels.hip + csrc/sma_seam.hip + csrc/stats_kernels.hip +
-  csrc/variable_rate_kernels.hip + csrc/clip_kernels.hip, linked against RCCL.
+  csrc/variable_rate_kernels.hip + csrc/clip_kernels.hip +
+  csrc/task_barrier_kernels.hip, linked against RCCL.
 * ``crossbow_amd/libGPU.so``           -- the JNI shim exporting Crossbow's
   ``TheGPU`` model-path natives; built only where ``jni.h`` exists (there is
   no JDK in this image).
@@ -34,7 +35,7 @@ def _hipcc() -> str:
 
 
 SOURCES = ("context.hip", "sync_steps.hip", "sma_kernels.hip", "averaging_kernels.hip", "sma_seam.hip",
-           "stats_kernels.hip", "variable_rate_kernels.hip", "clip_kernels.hip")
+           "stats_kernels.hip", "variable_rate_kernels.hip", "clip_kernels.hip", "task_barrier_kernels.hip")
 HEADERS = ("context_internal.h", "sma_internal.h", "stream_helpers.h", "stats_internal.h", "stats_plan.h",
            "optimise_plan.h", "clip_internal.h")
 

@@ -612,6 +612,20 @@ int cbx_merge(cbx_context *c, int pull, int *first_out) {
 
 static int default_step(cbx_context *c, int first);
 
+// What every barrier does once its step is enqueued: autotune, then the clock
+// of every locked replica.
+static int finish_barrier(cbx_context *c, int clock, int autotune) {
+  if (autotune < 0) TRY(cbx_del_model(c));
+  if (autotune > 0) TRY(cbx_add_model(c));
+  // modelmanager.c:259-265: clock of every locked replica.
+  for (int i = 0; i < c->size; ++i)
+    if (c->locked[i]) {
+      __atomic_store_n(&c->replicas[i]->clock, clock, __ATOMIC_RELEASE);  // read by cbx_get_next_or_wait
+      c->replicas[i]->updates = 0;
+    }
+  return CBX_OK;
+}
+
 // staged: 0 = device-resident step; > 0 = host-staged step over that many
 // buckets (cbx_synchronise_staged).
 static int synchronise_impl(cbx_context *c, int first, int clock, int autotune, int staged) {
@@ -648,15 +662,7 @@ static int synchronise_impl(cbx_context *c, int first, int clock, int autotune, 
     return fail(CBX_ERR_UNSUPPORTED,
                 "update model %d is not on this library's path (SMA, SYNCHRONOUSEAMSGD, POLYAK_RUPPERT, WORKER, DEFAULT)", type);
   }
-  if (autotune < 0) TRY(cbx_del_model(c));
-  if (autotune > 0) TRY(cbx_add_model(c));
-  // modelmanager.c:259-265: clock of every locked replica.
-  for (int i = 0; i < c->size; ++i)
-    if (c->locked[i]) {
-      __atomic_store_n(&c->replicas[i]->clock, clock, __ATOMIC_RELEASE);  // read by cbx_get_next_or_wait
-      c->replicas[i]->updates = 0;
-    }
-  return CBX_OK;
+  return finish_barrier(c, clock, autotune);
 }
 
 int cbx_synchronise(cbx_context *c, int first, int clock, int autotune, int push) {
@@ -668,6 +674,126 @@ int cbx_synchronise(cbx_context *c, int first, int clock, int autotune, int push
 int cbx_synchronise_staged(cbx_context *c, int first, int clock, int autotune, int buckets) {
   if (buckets < 1 || buckets > 4096) return fail(CBX_ERR_INVALID, "staged buckets must be 1..4096, got %d", buckets);
   return synchronise_impl(c, first, clock, autotune, buckets);
+}
+
+// The pending task steps of the locked replicas and the one-GPU SMA barrier in
+// one launch (task_barrier_kernels.hip).  Everything is validated before the
+// first side effect: a refused call leaves buffers, flags and clocks alone.
+int cbx_step_and_synchronise(cbx_context *c, int first, int clock, int autotune, const int *tasks, void *const *streams,
+                             unsigned flags) {
+  TraceRange trace("cbx_step_and_synchronise");
+  const char *me = "cbx_step_and_synchronise";
+  TRY(check_manager_q(c));
+  if (first < 0 || first > c->size) return fail(CBX_ERR_INVALID, "first replica %d out of range", first);
+  if (!tasks) return fail(CBX_ERR_INVALID, "%s: null task list (one entry per replica: a task number, or -1)", me);
+  if (flags & ~CBX_STEP_DISCARD_TASK_OUTPUTS) return fail(CBX_ERR_INVALID, "%s: unknown flag bits 0x%x", me, flags);
+  const int size = c->size;
+  for (int id = 0; id < size; ++id) {
+    if (tasks[id] < -1) return fail(CBX_ERR_INVALID, "%s: tasks[%d] = %d is neither a task number nor -1", me, id, tasks[id]);
+    if (tasks[id] < 0) continue;
+    if (c->replicas[id]->local < 0)
+      return fail(CBX_ERR_INVALID, "%s: stepping replica %d lives in another process (device %d)", me, id,
+                  c->replicas[id]->g);
+    if (!c->locked[id]) return fail(CBX_ERR_INVALID, "%s: stepping replica %d is not locked for this barrier", me, id);
+    if (id < first) return fail(CBX_ERR_INVALID, "%s: stepping replica %d is below the first replica %d", me, id, first);
+  }
+  if (c->G > 1 || c->devs.size() != 1)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: %d devices; the task steps are fused into the one-GPU barrier only, not into "
+                "kernel A of the split path", me, c->G > 1 ? c->G : (int)c->devs.size());
+  if (c->force_split)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: cbx_set_force_split is on; kernel A of the split path is not fused", me);
+  const int type = c->model.type;
+  if (type == CBX_UPDATE_SYNCHRONOUSEAMSGD && c->elastic_average)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: elastic averaging is on (cbx_set_elastic_average); only the SMA barrier is fused", me);
+  if (type != CBX_UPDATE_SMA && type != CBX_UPDATE_SYNCHRONOUSEAMSGD)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: update model %d; only SMA (7) and SYNCHRONOUSEAMSGD (3) are fused", me, type);
+  if (c->clip_on())
+    return fail(CBX_ERR_UNSUPPORTED, "%s: gradient clipping is on; the clipped step needs its norm pass first, use "
+                "cbx_replica_optimise and cbx_synchronise", me);
+  if (c->variable_rates && c->model.conf.irregular > 0)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: variable learning rates are on with %d irregular variables; use "
+                "cbx_replica_optimise and cbx_synchronise", me, c->model.conf.irregular);
+  Device &d = c->devs[0];
+  const SolverConf *ref = nullptr;  // the first stepping replica's configuration
+  int participating = 0;
+  for (int id : d.replicas) {
+    if (id < first || !c->locked[id]) continue;
+    ++participating;
+    if (tasks[id] < 0) continue;
+    const SolverConf &conf = c->replicas[id]->conf;
+    if (conf.momentum > 0 && conf.momentumMethod == 1)
+      return fail(CBX_ERR_UNSUPPORTED, "%s: replica %d: Nesterov's momentum has been disabled", me, id);  // sma.cu:46-48
+    if (!ref) ref = &conf;
+    if (conf.momentum != ref->momentum || conf.weightDecay != ref->weightDecay)
+      return fail(CBX_ERR_UNSUPPORTED, "%s: replica %d steps with momentum %g and weight decay %g, an earlier one with "
+                  "%g and %g; one launch takes one pair", me, id, (double)conf.momentum, (double)conf.weightDecay,
+                  (double)ref->momentum, (double)ref->weightDecay);
+    // what conf.learning_rate would refuse, before any replica's query has raised a flag
+    if (conf.policy == LR_STEP && conf.size <= 0) return fail(CBX_ERR_STATE, "step learning-rate policy with size 0");
+    if (conf.policy == LR_LSR && conf.warmuptasks <= 0) return fail(CBX_ERR_STATE, "LSR policy without warm-up tasks");
+    if (conf.policy == LR_CLR) return fail(CBX_ERR_UNSUPPORTED, "circular learning rate is unsupported");
+    if (conf.policy < LR_FIXED || conf.policy > LR_LSR)
+      return fail(CBX_ERR_UNSUPPORTED, "learning-rate policy %d unsupported", (int)conf.policy);
+  }
+  if (participating > cbx::kMaxReplicas)
+    return fail(CBX_ERR_UNSUPPORTED, "more than %d locked replicas on one device", cbx::kMaxReplicas);
+  if (ref && ref->momentum > 0 && !c->has_last)
+    return fail(CBX_ERR_STATE, "replica momentum without a `last` buffer (model.c:116-120)");
+
+  // The rates, in id order: a query may raise the replica's `_copy`
+  // (solverconfiguration.c:133,147), which this same call's Phase D honours.
+  std::vector<float> lr((size_t)size, 0.0f);
+  for (int id = 0; id < size; ++id)
+    if (tasks[id] >= 0) TRY(c->replicas[id]->conf.learning_rate(tasks[id], &lr[(size_t)id]));
+
+  cbx::TaskBarrierArgs a;
+  std::memset(&a, 0, sizeof(a));
+  int k = 0, copies = 0;
+  std::vector<hipStream_t> callers;
+  for (int id : d.replicas) {  // increasing id order, sma.c:69
+    if (id < first || !c->locked[id]) continue;
+    Replica &r = *c->replicas[id];
+    a.w[k] = reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_DATA));
+    a.s[k] = reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_DIFF));
+    if (tasks[id] >= 0) {
+      a.step_mask |= 1ull << k;
+      a.g[k] = reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_GRADIENT));
+      a.last[k] = r.conf.momentum > 0 ? reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_LAST)) : nullptr;
+      a.rate[k] = -lr[(size_t)id];  // sma.cu:43
+      hipStream_t st = streams && streams[id] ? reinterpret_cast<hipStream_t>(streams[id]) : d.stream;
+      if (st != d.stream && std::find(callers.begin(), callers.end(), st) == callers.end()) callers.push_back(st);
+    }
+    if (r.conf.copy) copies++;  // sma.c:113-120, after the queries
+    ++k;
+  }
+  a.nrep = k;
+  a.z = reinterpret_cast<cbx::v4f *>(base_dev(c, d, CBX_BUF_DATA));
+  const bool mom = c->has_last && c->model.conf.momentum > 0;  // sma.c:150 (base conf)
+  a.blast = mom ? reinterpret_cast<cbx::v4f *>(base_dev(c, d, CBX_BUF_LAST)) : nullptr;
+  a.n4 = c->n4;
+  a.alpha = c->model.conf.alpha;  // sma.c:33, theModel's conf
+  a.momentum = ref ? ref->momentum : 0.0f;
+  a.wd = ref ? ref->weightDecay : 0.0f;
+  a.copy = copies > 0 ? 1 : 0;
+
+  // The launch comes after the gradients: one deferred wait per caller stream,
+  // queued now, as cbx_synchronise queues the task steps' (DESIGN.md 7).
+  HIP_TRY(hipSetDevice(d.hip_id));
+  if (!c->fault_skip_task_wait)
+    for (hipStream_t st : callers) TRY(defer_task_wait(d, st));
+  TRY(flush_task_waits(c));
+  // A wait for a caller's stream now sits between the previous step and this
+  // launch: its start is a marker of its own, not that step's stop
+  // (step_start_event), as after cbx_replica_optimise on a task stream.
+  if (!callers.empty()) c->foreign_ops.fetch_add(1, std::memory_order_relaxed);
+
+  cbx::LaunchConfig cfg = c->task_barrier_cfg;
+  cfg.num_cus = d.num_cus;
+  HIP_TRY(cbx::launch_task_barrier(a, (flags & CBX_STEP_DISCARD_TASK_OUTPUTS) == 0, cfg, d.stream,
+                                   {step_start_event(c, d, 0), step_stop_event(c, d, EV_A)}));
+  close_fused_step(c, d);
+  TRY(finish_sma_step(c, first));
+  return finish_barrier(c, clock, autotune);
 }
 
 int cbx_unlock_any(cbx_context *c) {
@@ -1952,6 +2078,7 @@ int cbx_set_kernel_config(cbx_context *c, int block, int blocks_per_cu, int poli
   c->cfg.policy = policy;
   c->apply_cfg.policy = policy;  // load/store policy is shared; kernel B keeps its own geometry
   c->avg_cfg.policy = policy;    // and so do the averaging kernels
+  c->task_barrier_cfg.policy = policy;  // and the task steps fused into the barrier
   c->cfg.unroll = unroll;
   return CBX_OK;
 }
@@ -2014,6 +2141,19 @@ int cbx_set_averaging_kernel_config(cbx_context *c, int block, int unroll, int w
   c->avg_cfg.block = block;
   c->avg_cfg.unroll = unroll;
   c->avg_cfg.waves_per_cu = waves_per_cu;
+  return CBX_OK;
+}
+
+int cbx_set_task_barrier_kernel_config(cbx_context *c, int block, int unroll, int waves_per_cu) {
+  TRY(check_ctx(c));
+  if (block < 64 || block > 256 || block % 64 != 0) return fail(CBX_ERR_INVALID, "block must be 64..256, multiple of 64");
+  if (unroll != 1 && unroll != 2) return fail(CBX_ERR_INVALID, "unroll must be 1 or 2");
+  if ((int64_t)block * unroll > cbx::kPadFloat4 || cbx::kPadFloat4 % ((int64_t)block * unroll) != 0)
+    return fail(CBX_ERR_INVALID, "block*unroll must divide %lld", (long long)cbx::kPadFloat4);
+  if (waves_per_cu < -1 || waves_per_cu > 32) return fail(CBX_ERR_INVALID, "waves per CU must be -1 (auto) or 0..32");
+  c->task_barrier_cfg.block = block;
+  c->task_barrier_cfg.unroll = unroll;
+  c->task_barrier_cfg.waves_per_cu = waves_per_cu;
   return CBX_OK;
 }
 

@@ -544,6 +544,8 @@ struct cbx_context {
   cbx::LaunchConfig avg_cfg = cbx::averaging_launch_config();
   // Kernel B of the split SMA path (scripts/apply_sweep.py).
   cbx::LaunchConfig apply_cfg = cbx::sma_apply_launch_config();
+  // The task steps fused into the barrier (cbx_step_and_synchronise).
+  cbx::LaunchConfig task_barrier_cfg = cbx::task_barrier_launch_config();
   int64_t bucket_elems = 0;
   bool force_split = false;
   bool elastic_average = false;  // cbx_set_elastic_average: update model 3 runs EA-SGD, not SMA
@@ -1077,6 +1079,11 @@ cbx::SmaArgs offset_args(const cbx::SmaArgs &a, int64_t start4, int64_t len4);
 // SMA (synch/sma.c:13-231): fused at G = 1; kernel A / collective / kernel B
 // per bucket at G > 1 (or forced); the peer-read form.
 int sma_step(cbx_context *c, int first);
+// What sma_step's fused form does after its launch, shared with
+// cbx_step_and_synchronise: the ring slot and the pipeline state, then the
+// step event and the `_copy` reset.
+void close_fused_step(cbx_context *c, Device &d);
+int finish_sma_step(cbx_context *c, int first);
 // The same step from and to the pinned host mirror (cbx_synchronise_staged).
 int sma_step_staged(cbx_context *c, int first, int buckets);
 // Synchronous SGD, update model WORKER (synch/synchronoussgd.c:13-106).

@@ -339,6 +339,43 @@ hipError_t launch_sma_optimise_variables(const VarTables &t, VarOptArgs a, const
 hipError_t var_tables_upload(VarTables &t, const uint32_t *chunks, size_t nchunks, const uint32_t *bounds,
                              const float *mult, uint32_t nvars);
 void var_tables_free(VarTables &t);
+// The replicas' pending task steps fused into the one-GPU SMA barrier
+// (cbx_step_and_synchronise, task_barrier_kernels.hip): launch_sma_optimise on
+// every replica whose step_mask bit is set, then launch_sma_fused, in one pass
+// over the context's padded buffers.  About 2.4 KB of kernel arguments.
+struct TaskBarrierArgs {
+  v4f *w[kMaxReplicas];     // participating replicas, id order: replica->data
+  v4f *s[kMaxReplicas];     // replica->diff: read if the replica only joins, written (KEEP) if it steps
+  v4f *g[kMaxReplicas];     // replica->gradient (stepping replicas)
+  v4f *last[kMaxReplicas];  // replica->last (stepping replicas, momentum > 0)
+  float rate[kMaxReplicas]; // -learning rate of the replica's task (sma.cu:43)
+  v4f *z;                   // base->data
+  v4f *blast;               // base->last; null: no base momentum
+  int64_t n4;               // float4s (multiple of kPadFloat4)
+  uint64_t step_mask;       // bit k: participating replica k steps
+  float alpha;              // conf->alpha (sma.c:33)
+  float momentum;           // the stepping replicas' conf->momentum
+  float wd;                 // the stepping replicas' conf->weightDecay
+  int nrep;
+  int copy;                 // Phase D: some participating replica asked for a copy
+  int pad_;
+};
+// keep_task_outputs: s and g of the stepping replicas are written as
+// launch_sma_optimise writes them; otherwise they are not touched.
+hipError_t launch_task_barrier(const TaskBarrierArgs &a, bool keep_task_outputs, const LaunchConfig &cfg,
+                               hipStream_t stream, Timing t = {});
+// One-wave blocks, one float4 per lane, auto occupancy (2 waves per CU at
+// R = 8): at the SMA step's own shape, two float4s per lane, it measured 2-5 %
+// slower in each of three runs (scripts/bench_step_and_synchronise.py --sweep,
+// profiles/task_barrier/).  cbx_set_task_barrier_kernel_config
+// overrides it.
+inline LaunchConfig task_barrier_launch_config() {
+  LaunchConfig c;
+  c.block = 64;
+  c.unroll = 1;
+  c.waves_per_cu = -1;
+  return c;
+}
 // DEFAULT update model (0, kernels/optimisers/default.cu:3-131): the task
 // step moves the replica and its device's base model by the same gradient.
 // Reads w, g (, last), z; writes g (if changed), last, w, z.

@@ -1261,6 +1261,27 @@ struct SplitStep {
   }
 };
 
+// After the one launch of a fused one-device step, timestamped by
+// step_start_event / step_stop_event(EV_A): its ring slot is closed, and the
+// next split step continues from nothing.
+void close_fused_step(cbx_context *c, Device &d) {
+  ring_advance(c, d, 0);
+  d.cross_valid = false;
+  c->last_step_split = false;
+}
+
+// The end of an SMA step of any form: the step event, and `_copy` of the
+// locked replicas from `first` on.
+int finish_sma_step(cbx_context *c, int first) {
+  TRY(finish_step(c));
+  for (Device &d : c->devs)
+    for (int id : d.replicas) {
+      if (id < first || !c->locked[id]) continue;
+      c->replicas[id]->conf.copy = 0;  // sma.c:220 (a no-op unless a copy happened)
+    }
+  return CBX_OK;
+}
+
 int sma_step(cbx_context *c, int first) {
   const bool mom = c->has_last && c->model.conf.momentum > 0;  // sma.c:150 (base conf)
   std::vector<cbx::SmaArgs> args(c->devs.size());
@@ -1285,9 +1306,7 @@ int sma_step(cbx_context *c, int first) {
     // events: no marker packets between back-to-back steps.
     HIP_TRY(cbx::launch_sma_fused(args[0], mom, copies_total > 0, cfg, d.stream,
                                   {step_start_event(c, d, 0), step_stop_event(c, d, EV_A)}));
-    ring_advance(c, d, 0);
-    d.cross_valid = false;
-    c->last_step_split = false;
+    close_fused_step(c, d);
   } else {
     SplitStep split(c, args, mom);
     const int rc = split.run();
@@ -1309,13 +1328,7 @@ int sma_step(cbx_context *c, int first) {
     }
   }
 
-  TRY(finish_step(c));
-  for (Device &d : c->devs)
-    for (int id : d.replicas) {
-      if (id < first || !c->locked[id]) continue;
-      c->replicas[id]->conf.copy = 0;  // sma.c:220 (a no-op unless a copy happened)
-    }
-  return CBX_OK;
+  return finish_sma_step(c, first);
 }
 
 // ---------------------------------------------------------------------------

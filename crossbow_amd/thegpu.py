@@ -200,6 +200,29 @@ class TheGPU:
         in, host mirrors out; include/crossbow_sma.h)."""
         return check(self._L.cbx_synchronise_staged(self._ctx, first, clock, autotune, buckets))
 
+    def step_and_synchronise(self, first: int, clock: int, autotune: int, tasks: Sequence[int],
+                             streams: Optional[Sequence[Optional[int]]] = None, flags: int = 0) -> int:
+        """``cbx_step_and_synchronise``: the pending task steps of the locked
+        replicas and the one-GPU SMA barrier in one launch.
+
+        ``tasks[id]`` is replica id's task number, or -1 when it only joins the
+        barrier; ``streams[id]`` the raw hipStream_t its gradient was produced
+        on (None: the sync stream).  ``flags`` may be
+        ``STEP_DISCARD_TASK_OUTPUTS`` (include/crossbow_sma.h has the promise
+        that goes with it)."""
+        tasks = list(tasks)
+        N = self.num_replicas()
+        if len(tasks) != N:
+            raise ValueError(f"one task entry per replica ({N}) expected, got {len(tasks)}")
+        ta = (ctypes.c_int * max(1, N))(*tasks)
+        sa = None
+        if streams is not None:
+            streams = list(streams)
+            if len(streams) != N:
+                raise ValueError(f"one stream entry per replica ({N}) expected, got {len(streams)}")
+            sa = (ctypes.c_void_p * max(1, N))(*[s if s else None for s in streams])
+        return check(self._L.cbx_step_and_synchronise(self._ctx, first, clock, autotune, ta, sa, flags))
+
     def unlockAny(self) -> int:
         return check(self._L.cbx_unlock_any(self._ctx))
 
@@ -482,6 +505,10 @@ class TheGPU:
 
     def set_averaging_kernel_config(self, block: int = 64, unroll: int = 1, waves_per_cu: int = -1) -> None:
         check(self._L.cbx_set_averaging_kernel_config(self._ctx, block, unroll, waves_per_cu))
+
+    def set_task_barrier_kernel_config(self, block: int = 64, unroll: int = 1, waves_per_cu: int = -1) -> None:
+        """Launch geometry of ``step_and_synchronise``'s kernel."""
+        check(self._L.cbx_set_task_barrier_kernel_config(self._ctx, block, unroll, waves_per_cu))
 
     def set_pipeline_mode(self, mode: int) -> None:
         """0: buckets overlap within a step; 1: also across steps."""

@@ -201,6 +201,51 @@ int cbx_synchronise (cbx_context *ctx, int first, int clock, int autotune, int p
  * the three calls unpipelined, and so do elastic averaging and
  * POLYAK_RUPPERT.                                                         */
 int cbx_synchronise_staged (cbx_context *ctx, int first, int clock, int autotune, int buckets);
+/* The replicas' pending task steps and the one-GPU SMA barrier in one pass
+ * over memory.  With tau = 1 every task step is followed by a barrier before
+ * the replica is read again; the two calls read and write each w_i twice and
+ * pass s_i through memory only for the barrier to read it back.
+ *
+ * tasks[id], one entry for every id in 0..cbx_num_replicas: >= 0 means replica
+ * id holds a gradient in `g` that has not been applied; the call takes its
+ * step for that task number and then averages it.  -1 means the replica takes
+ * part in the barrier as it does in cbx_synchronise, with its s and w as they
+ * are.  streams[id] is the stream on which replica id's `g` was produced; an
+ * entry may be NULL (the sync stream), and so may `streams` itself.  The launch
+ * is ordered behind every such stream the way cbx_synchronise is ordered behind
+ * cbx_replica_optimise on a task stream.  Asynchronous like cbx_synchronise.
+ *
+ * The contract.  With flags == 0 the call leaves every buffer (z, the base
+ * `last`, every w_i, last_i, s_i and g_i) bit for bit, and every piece of host
+ * state (copy flags, clocks, `updates`, the step event, one timing-history
+ * entry), as if the caller had made
+ *   cbx_replica_optimise (ctx, id, tasks[id], streams[id])  for every id with
+ *                                                           tasks[id] >= 0,
+ *   cbx_synchronise (ctx, first, clock, autotune, 0).
+ * A learning-rate query that raises a replica's copy flag (MULTISTEP at its
+ * boundary) triggers Phase D in this same call, as it does in the sequence.
+ *
+ * With CBX_STEP_DISCARD_TASK_OUTPUTS, s_i and g_i of the stepping replicas are
+ * not written at all (they keep what they held); everything else is as above.
+ * In return the caller promises that such a replica steps again, through
+ * either call, before it next joins a barrier with tasks[id] == -1 (or through
+ * cbx_synchronise), and before anyone reads its s or g: cbx_model_stats with
+ * CBX_BUF_DIFF or CBX_BUF_GRADIENT, cbx_replica_read of them, or a step
+ * through the sma.c seam on those buffers.
+ *
+ * Everything is checked before the first side effect: a refused call changes
+ * no buffer, flag or clock, and cbx_last_error names the cause.
+ * CBX_ERR_INVALID: tasks is NULL; a tasks[id] < -1; an unknown flag bit; a
+ * stepping replica that is not local, not locked (cbx_lock_any) or below
+ * `first`.  CBX_ERR_UNSUPPORTED: more than one device, or cbx_set_force_split
+ * on (kernel A of the split path is not fused); an update model other than SMA
+ * (7) or SYNCHRONOUSEAMSGD (3) without elastic averaging; gradient clipping on;
+ * cbx_set_variable_learning_rates on with a multiplier that is not 1; Nesterov
+ * momentum on a stepping replica; stepping replicas whose momentum or weight
+ * decay differ.  CBX_ERR_STATE: replica momentum without a `last` buffer.   */
+#define CBX_STEP_DISCARD_TASK_OUTPUTS 1u
+int cbx_step_and_synchronise (cbx_context *ctx, int first, int clock, int autotune,
+                              const int *tasks, void *const *streams, unsigned flags);
 /* TheGPU.unlockAny() GPU.c:1142-1149 -> modelmanager.c:233-245           */
 int cbx_unlock_any (cbx_context *ctx);
 
@@ -569,6 +614,12 @@ int cbx_set_apply_kernel_config (cbx_context *ctx, int block, int unroll, int wa
  * G > 1 follows cbx_set_apply_kernel_config, and all of them the load/store
  * policy of cbx_set_kernel_config.                                         */
 int cbx_set_averaging_kernel_config (cbx_context *ctx, int block, int unroll, int waves_per_cu);
+/* Launch geometry of cbx_step_and_synchronise's kernel (3R + 2 reads and
+ * 2R + 2 or 4R + 2 writes per element with momentum): block 64..256, unroll
+ * 1 or 2, occupancy cap as above.  Default 64 / 1 / auto (2 waves per CU at
+ * R = 8, measured: scripts/bench_step_and_synchronise.py --sweep); the
+ * load/store policy is cbx_set_kernel_config's.                            */
+int cbx_set_task_barrier_kernel_config (cbx_context *ctx, int block, int unroll, int waves_per_cu);
 /* Bucketed pipeline for G > 1: kernel A / all-reduce / kernel B per bucket
  * of `bucket_elements` floats; 0 (default) = 8 buckets when G > 1, one at
  * G = 1; a value >= n = one bucket, all in order on the sync stream.  With
