@@ -192,6 +192,8 @@ SIGNATURES = {
     "cbx_sma_plan_set_timing": (_I, [_P, _I]),
     "cbx_sma_plan_timing_history": (_I, [_P, _FP, _I]),
     "cbx_sma_plan_step": (_I, [_P, _PP, _PP, _PP, _I, _IP, _PP, _PP, _IP, _IP, _F, _F, _I]),
+    "cbx_sma_plan_step_and_optimise": (_I, [_P, _PP, _PP, _PP, _I, _IP, _PP, _PP, _PP, _PP, _IP, _IP, _IP, _FP,
+                                            _F, _F, _F, _F, _I, _c.c_uint]),
     "cbx_sma_plan_buffer_stats": (_I, [_P, _I, _P, _P, _PP, _I, _LLP, _I, _BS, _BS, _BS, _BS]),
     "cbx_sma_optimise_buffers": (_I, [_P, _P, _P, _P, _P, _c.c_longlong, _F, _F, _F]),
     "cbx_sma_plan_set_variables": (_I, [_P, _LLP, _FP, _I]),

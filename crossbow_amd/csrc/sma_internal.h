@@ -342,7 +342,8 @@ void var_tables_free(VarTables &t);
 // The replicas' pending task steps fused into the one-GPU SMA barrier
 // (cbx_step_and_synchronise, task_barrier_kernels.hip): launch_sma_optimise on
 // every replica whose step_mask bit is set, then launch_sma_fused, in one pass
-// over the context's padded buffers.  About 2.4 KB of kernel arguments.
+// over the context's padded buffers, or over buffers the caller owns
+// (cbx_sma_plan_step_and_optimise).  About 2.4 KB of kernel arguments.
 struct TaskBarrierArgs {
   v4f *w[kMaxReplicas];     // participating replicas, id order: replica->data
   v4f *s[kMaxReplicas];     // replica->diff: read if the replica only joins, written (KEEP) if it steps
@@ -351,7 +352,7 @@ struct TaskBarrierArgs {
   float rate[kMaxReplicas]; // -learning rate of the replica's task (sma.cu:43)
   v4f *z;                   // base->data
   v4f *blast;               // base->last; null: no base momentum
-  int64_t n4;               // float4s (multiple of kPadFloat4)
+  int64_t n4;               // float4s (whole 64 x unroll chunks; the context's: kPadFloat4s)
   uint64_t step_mask;       // bit k: participating replica k steps
   float alpha;              // conf->alpha (sma.c:33)
   float momentum;           // the stepping replicas' conf->momentum
@@ -359,9 +360,16 @@ struct TaskBarrierArgs {
   int nrep;
   int copy;                 // Phase D: some participating replica asked for a copy
   int pad_;
+  int64_t tail_lo, tail_hi;  // caller-owned buffers: elements past the last whole trip (see SmaArgs)
+  int tail_blocks;
 };
 // keep_task_outputs: s and g of the stepping replicas are written as
-// launch_sma_optimise writes them; otherwise they are not touched.
+// launch_sma_optimise writes them; otherwise they are not touched (and a
+// stepping replica's s may be null).  a.n4 == 0 with a tail range launches the
+// tail workgroups only.  A tail range needs cfg.policy == 1: only the
+// nontemporal TAIL instantiations exist, any other policy is
+// hipErrorInvalidValue.  So is a block that is no multiple of 64, or an n4 that
+// is no whole number of 64 x unroll chunks (the context's always is).
 hipError_t launch_task_barrier(const TaskBarrierArgs &a, bool keep_task_outputs, const LaunchConfig &cfg,
                                hipStream_t stream, Timing t = {});
 // One-wave blocks, one float4 per lane, auto occupancy (2 waves per CU at

@@ -4,6 +4,7 @@
 // function bodies:
 //   crossbowSynchronisationSMA (clib-multigpu/synch/sma.c:233-248 -> :13-231)
 //   crossbowKernelOptimiserSMA (kernels/optimisers/sma.cu:3-100)
+//   (the two in one launch for a tau = 1 build: cbx_sma_plan_step_and_optimise)
 //   crossbowSynchronisationSynchronousSGD (synch/synchronoussgd.c:13-106)
 //   crossbowKernelOptimiserSynchronousSGD (kernels/optimisers/synchronoussgd.cu:3-56)
 //   crossbowSynchronisationSynchronousElasticAveragingSGD
@@ -101,6 +102,7 @@ struct cbx_sma_plan {
   cbx::LaunchConfig apply_cfg = cbx::sma_apply_launch_config();
   cbx::LaunchConfig ssgd_apply_cfg = cbx::ssgd_apply_launch_config();
   cbx::LaunchConfig avg_cfg = cbx::averaging_launch_config();  // cbx_ea_plan_step / cbx_pr_plan_step: fused and kernel A
+  cbx::LaunchConfig task_barrier_cfg = cbx::task_barrier_launch_config();  // cbx_sma_plan_step_and_optimise
   // cbx_sma_plan_set_timing: the one-rank fused launches stamp their own start
   // and stop into a ring of kTimedSteps event pairs (no marker packets).
   static constexpr int kTimedSteps = 256;
@@ -567,6 +569,90 @@ int cbx_sma_plan_step(cbx_sma_plan *p, void *const *streams, float *const *z, fl
   }
   TRY(apply(nb - 1));
   return copies_total > 0 ? 1 : 0;
+}
+
+// crossbowKernelOptimiserSMA of every stepping replica and
+// crossbowSynchronisationSMA in one launch over the caller's buffers: the
+// context's cbx_step_and_synchronise (context.hip) with the caller's rates,
+// flags and stream order.  One device, one rank: kernel A of the split path is
+// not fused.  The bulk runs the context's float4 loop, the elements past it the
+// kernel's TAIL workgroups (task_barrier_kernels.hip).  Everything is
+// validated before the launch; the plan queues no wait of its own.
+int cbx_sma_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *const *z, float *const *last,
+                                   int nreplicas, const int *replica_device, float *const *w, float *const *s,
+                                   float *const *g, float *const *rlast, const int *locked, const int *copy,
+                                   const int *step, const float *learning_rate, float alpha, float momentum,
+                                   float replica_momentum, float weight_decay, int first, unsigned flags) {
+  TraceRange trace("cbx_sma_plan_step_and_optimise");
+  const char *me = "cbx_sma_plan_step_and_optimise";
+  if (!p) return fail(CBX_ERR_INVALID, "null plan");
+  if (!streams || !z || nreplicas < 0 ||
+      (nreplicas > 0 && (!replica_device || !w || !s || !g || !locked || !copy || !step || !learning_rate)))
+    return fail(CBX_ERR_INVALID, "%s: missing arguments", me);
+  if (flags & ~CBX_STEP_DISCARD_TASK_OUTPUTS) return fail(CBX_ERR_INVALID, "%s: unknown flag bits 0x%x", me, flags);
+  if (first < 0 || first > nreplicas) return fail(CBX_ERR_INVALID, "%s: first replica %d out of range", me, first);
+  const bool keep = (flags & CBX_STEP_DISCARD_TASK_OUTPUTS) == 0;
+  const bool mom = momentum > 0.0f;           // sma.c:150: base momentum forced to 0.9 when > 0
+  const bool rmom = replica_momentum > 0.0f;  // sma.cu:45
+  if (mom && !last) return fail(CBX_ERR_INVALID, "%s: base momentum > 0 needs the base model's last buffer", me);
+  for (int id = 0; id < nreplicas; ++id) {
+    if (!step[id]) continue;
+    if (!locked[id]) return fail(CBX_ERR_INVALID, "%s: stepping replica %d is not locked for this barrier", me, id);
+    if (id < first) return fail(CBX_ERR_INVALID, "%s: stepping replica %d is below the first replica %d", me, id, first);
+    if (rmom && !rlast) return fail(CBX_ERR_INVALID, "%s: replica momentum > 0 needs the replicas' last buffers", me);
+  }
+  if (p->devs.size() != 1 || p->ranks != 1)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: a plan of %d devices and %d ranks; the task steps are fused into the one-GPU "
+                "barrier only, not into kernel A of the split path", me, (int)p->devs.size(), p->ranks);
+  if (!z[0] || !aligned16(z[0]) || (mom && (!last[0] || !aligned16(last[0]))))
+    return fail(CBX_ERR_INVALID, "%s: base buffers must be non-null and 16-byte aligned", me);
+  cbx::TaskBarrierArgs a;
+  std::memset(&a, 0, sizeof(a));
+  int copies = 0, participating = 0;
+  bool steps = false;
+  for (int id = first; id < nreplicas; ++id) {  // increasing id order, sma.c:69
+    if (!locked[id]) continue;
+    if (replica_device[id] != 0) return fail(CBX_ERR_INVALID, "%s: replica %d on device %d of 1", me, id, replica_device[id]);
+    const bool st = step[id] != 0;
+    if (!w[id] || !aligned16(w[id])) return fail(CBX_ERR_INVALID, "%s: replica %d: w must be non-null and 16-byte aligned", me, id);
+    // a stepping replica's s is only written, and not at all under the discard flag
+    if ((!s[id] && (!st || keep)) || !aligned16(s[id]))
+      return fail(CBX_ERR_INVALID, "%s: replica %d: s must be non-null and 16-byte aligned", me, id);
+    if (st && (!g[id] || !aligned16(g[id])))
+      return fail(CBX_ERR_INVALID, "%s: stepping replica %d: g must be non-null and 16-byte aligned", me, id);
+    if (st && rmom && (!rlast[id] || !aligned16(rlast[id])))
+      return fail(CBX_ERR_INVALID, "%s: stepping replica %d: replica momentum > 0 needs a 16-byte aligned last buffer", me, id);
+    if (++participating > cbx::kMaxReplicas) continue;  // counted on, refused below
+    const int k = a.nrep++;
+    a.w[k] = reinterpret_cast<cbx::v4f *>(w[id]);
+    a.s[k] = reinterpret_cast<cbx::v4f *>(s[id]);
+    if (st) {
+      steps = true;
+      a.step_mask |= 1ull << k;
+      a.g[k] = reinterpret_cast<cbx::v4f *>(g[id]);
+      a.last[k] = rmom ? reinterpret_cast<cbx::v4f *>(rlast[id]) : nullptr;
+      a.rate[k] = -1.0f * learning_rate[id];  // sma.cu:43
+    }
+    if (copy[id]) ++copies;  // sma.c:113-120
+  }
+  if (participating > cbx::kMaxReplicas)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: %d participating replicas, more than %d on one device", me, participating,
+                cbx::kMaxReplicas);
+  a.z = reinterpret_cast<cbx::v4f *>(z[0]);
+  a.blast = mom ? reinterpret_cast<cbx::v4f *>(last[0]) : nullptr;
+  a.n4 = p->n4b;
+  a.alpha = alpha;  // sma.c:33
+  a.momentum = steps && rmom ? replica_momentum : 0.0f;
+  a.wd = steps && weight_decay > 0.0f ? weight_decay : 0.0f;
+  a.copy = copies > 0 ? 1 : 0;
+  a.tail_lo = p->n4b * 4;  // the elements past the last whole chunk ride the same launch
+  a.tail_hi = p->n;
+  auto &d = p->devs[0];
+  HIP_TRY(hipSetDevice(d.hip_id));
+  cbx::LaunchConfig cfg = p->task_barrier_cfg;
+  cfg.num_cus = d.num_cus;
+  HIP_TRY(cbx::launch_task_barrier(a, keep, cfg, static_cast<hipStream_t>(streams[0]), p->next_timing()));
+  return copies > 0 ? 1 : 0;
 }
 
 // crossbowSynchronisationSynchronousSGD (synch/synchronoussgd.c:13-106) over

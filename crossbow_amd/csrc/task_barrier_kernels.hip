@@ -12,8 +12,9 @@
 //
 // One streaming pass in the shape of the kernels it fuses: 16-byte float4s per
 // lane behind an SGPR base and a 32-bit offset, every load of a replica chunk
-// issued before the first arithmetic, acc in registers, no LDS, no tail (the
-// context's buffers are padded to kPadFloat4).
+// issued before the first arithmetic, acc in registers, no LDS.  The context's
+// buffers are padded to kPadFloat4 and need no tail; buffers the caller owns
+// (cbx_sma_plan_step_and_optimise) take the TAIL instantiations.
 //
 // Arithmetic is the two kernels', one fp32 operation per reference call, in
 // their order (built with -ffp-contract=off): for a stepping replica i
@@ -38,6 +39,80 @@ static_assert(kMaxReplicas <= 64, "step_mask holds one bit per replica");
 
 namespace {
 
+// Buffers the caller owns (the sma.c seam, sma_seam.hip) hold exactly n
+// floats.  Their last elements [a.tail_lo, a.tail_hi) go to the first
+// a.tail_blocks workgroups of the same launch (TAIL instantiations), one float
+// per lane, as in the SMA kernels (sma_tail_elem, sma_kernels.hip): the fp32
+// sequence per element, the per-replica choice by a.step_mask (set for every
+// replica in the all-step forms too), the chunked replica walk and Phase D are
+// those of the float4 path below.
+template <bool MOM, bool BMOM, bool WD, bool KEEP>
+__device__ __forceinline__ void task_barrier_tail_elem(const TaskBarrierArgs &a) {
+  const int64_t i = a.tail_lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.tail_hi) return;
+  float *z = reinterpret_cast<float *>(a.z);
+  float z0 = z[i];
+  float l0 = 0.0f;
+  if constexpr (BMOM) l0 = reinterpret_cast<const float *>(a.blast)[i];
+  float acc = 0.0f;  // sma.c:66
+  for (int c = 0; c < a.nrep; c += kChunk) {
+    // a stepping replica: x = w, y = g, l = last_i; one that only joins: x = s, y = w
+    float x[kChunk], y[kChunk];
+    [[maybe_unused]] float l[kChunk];
+    // every load of a chunk issued before its first store (sma_tail_elem)
+#pragma unroll
+    for (int r = 0; r < kChunk; ++r) {
+      if (c + r < a.nrep) {
+        const bool step = ((a.step_mask >> (c + r)) & 1ull) != 0;
+        x[r] = reinterpret_cast<const float *>(step ? a.w[c + r] : a.s[c + r])[i];
+        y[r] = reinterpret_cast<const float *>(step ? a.g[c + r] : a.w[c + r])[i];
+        if constexpr (MOM) {
+          if (step) l[r] = reinterpret_cast<const float *>(a.last[c + r])[i];
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < kChunk; ++r) {
+      if (c + r < a.nrep) {
+        const bool step = ((a.step_mask >> (c + r)) & 1ull) != 0;
+        const float sv = x[r];
+        float wn;
+        if (step) {
+          const float rate = a.rate[c + r];
+          float gv = y[r];
+          if constexpr (WD) gv = fmaf(a.wd, sv, gv);  // sma.cu:24-31
+          if constexpr (MOM) {
+            gv = rate * gv;                    // :52-56
+            gv = fmaf(a.momentum, l[r], gv);   // :59-64
+            reinterpret_cast<float *>(a.last[c + r])[i] = gv;  // :68
+            wn = fmaf(1.0f, gv, sv);           // :74
+          } else {
+            wn = fmaf(rate, gv, sv);  // :90
+          }
+          if constexpr (KEEP) {
+            reinterpret_cast<float *>(a.s[c + r])[i] = sv;  // :71 / :87
+            if constexpr (MOM || WD) reinterpret_cast<float *>(a.g[c + r])[i] = gv;
+          }
+        } else {
+          wn = y[r];
+        }
+        const float d = fmaf(-1.0f, z0, sv);                             // sma.c:79-90
+        acc = fmaf(a.alpha, d, acc);                                     // :102-107
+        reinterpret_cast<float *>(a.w[c + r])[i] = fmaf(-a.alpha, d, wn);  // :93-99
+      }
+    }
+  }
+  float D = acc;
+  if constexpr (BMOM) {
+    D = fmaf(kBaseMomentum, l0, D);  // sma.c:155-164
+    reinterpret_cast<float *>(a.blast)[i] = D;
+  }
+  z0 = fmaf(1.0f, D, z0);  // sma.c:169-174
+  z[i] = z0;
+  if (a.copy != 0)
+    for (int r = 0; r < a.nrep; ++r) reinterpret_cast<float *>(a.w[r])[i] = z0;  // sma.c:185-227
+}
+
 // R > 0: that many replicas, fully unrolled (R <= kChunk); R == -1 takes
 // a.nrep and walks the replicas in register-resident chunks of kChunk.
 // MIXED: a.step_mask says which replicas step (a wave-uniform branch per
@@ -45,15 +120,24 @@ namespace {
 // momentum and weight decay; BMOM: the base model's momentum (a.blast).
 // KEEP: s_i and g_i of the stepping replicas are written as the plain step
 // writes them; otherwise they are not touched.  a.copy is wave-uniform too.
-template <int R, bool MIXED, bool MOM, bool BMOM, bool WD, bool KEEP, int P, int U>
+// TAIL: the launch's first a.tail_blocks workgroups do the caller's last
+// elements (task_barrier_tail_elem); without it the kernel is the context's.
+template <int R, bool MIXED, bool MOM, bool BMOM, bool WD, bool KEEP, int P, bool TAIL, int U>
 __global__ __launch_bounds__(256) void task_barrier_kernel(const TaskBarrierArgs a) {
   constexpr int RR = (R > 0) ? R : kChunk;
-  const uint32_t trip = gridDim.x * blockDim.x * U;
+  if constexpr (TAIL) {
+    if (blockIdx.x < (uint32_t)a.tail_blocks) {
+      task_barrier_tail_elem<MOM, BMOM, WD, KEEP>(a);
+      return;
+    }
+  }
+  const uint32_t tb = TAIL ? (uint32_t)a.tail_blocks : 0u;
+  const uint32_t trip = (gridDim.x - tb) * blockDim.x * U;
   const uint32_t n4 = (uint32_t)a.n4;
   const v4f al = a.alpha, nal = -a.alpha, mb = kBaseMomentum, one = 1.0f, mone = -1.0f;
   const v4f mu = a.momentum, wd = a.wd;
   const bool copy = a.copy != 0;
-  for (uint32_t base = first_elem<U>(); base < n4; base += trip) {
+  for (uint32_t base = first_elem<U>(blockIdx.x - tb); base < n4; base += trip) {
     v4f zv[U], lv[U], acc[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -145,7 +229,17 @@ __global__ __launch_bounds__(256) void task_barrier_kernel(const TaskBarrierArgs
 template <int R, bool MIXED, bool MOM, bool BMOM, bool WD, bool KEEP, int P>
 hipError_t tb_u(const TaskBarrierArgs &a, const LaunchConfig &cfg0, hipStream_t s, Timing t) {
   const LaunchConfig cfg = small_launch_shape(cfg0, a.n4);
-  const dim3 g = grid_for(a.n4, cfg);
+  const bool tail = a.tail_hi > a.tail_lo;
+  // Every wave's chunk (64 lanes x unroll float4s, first_elem) is whole, so no
+  // bounds check sits in the kernel's loop.  The context's padded buffers are
+  // whole kPadFloat4s; the bulk of a caller-owned buffer is whole chunks only
+  // (e.g. 1,280 float4s), and may be empty when a tail is all there is.  The
+  // check stands in front of the context's launches too, which had none: the
+  // arena's whole kPadFloat4s and the setter's shapes always pass it.
+  if (cfg.block <= 0 || cfg.block % 64 != 0 || cfg.unroll < 1 || a.n4 < 0 || a.n4 % (64ll * cfg.unroll) != 0 ||
+      (a.n4 == 0 && !tail))
+    return hipErrorInvalidValue;
+  dim3 g = a.n4 > 0 ? grid_for(a.n4, cfg) : dim3(0);
   // Buffer streams per lane: a stepping replica reads w, g (, last_i) and
   // writes w (, last_i) (, s, g); one that only joins reads s, w and writes w.
   int steps = 0;
@@ -153,13 +247,32 @@ hipError_t tb_u(const TaskBarrierArgs &a, const LaunchConfig &cfg0, hipStream_t 
   const int joins = a.nrep - steps;
   const int reads = 1 + (BMOM ? 1 : 0) + steps * (2 + (MOM ? 1 : 0)) + joins * 2;
   const int writes = 1 + (BMOM ? 1 : 0) + steps * (1 + (MOM ? 1 : 0) + (KEEP ? 1 + ((MOM || WD) ? 1 : 0) : 0)) + joins;
+  // the cap is sized by the bulk's grid: the few tail workgroups are not counted
   const unsigned lds = lds_for_occupancy(cfg, reads, writes, g.x);
+  if (tail) {  // caller-owned buffers: the tail rides the same launch, in front (nontemporal policy only)
+    if constexpr (P != 1) {
+      return hipErrorInvalidValue;
+    } else {
+      TaskBarrierArgs b = a;
+      b.tail_blocks = (int)((b.tail_hi - b.tail_lo + cfg.block - 1) / cfg.block);
+      g.x += (unsigned)b.tail_blocks;
+      if (cfg.unroll == 2)
+        hipExtLaunchKernelGGL((task_barrier_kernel<R, MIXED, MOM, BMOM, WD, KEEP, P, true, 2>), g, dim3(cfg.block), lds, s,
+                              t.start, t.stop, 0, b);
+      else if (cfg.unroll == 1)
+        hipExtLaunchKernelGGL((task_barrier_kernel<R, MIXED, MOM, BMOM, WD, KEEP, P, true, 1>), g, dim3(cfg.block), lds, s,
+                              t.start, t.stop, 0, b);
+      else
+        return hipErrorInvalidValue;
+      return hipGetLastError();
+    }
+  }
   if (cfg.unroll == 2)
-    hipExtLaunchKernelGGL((task_barrier_kernel<R, MIXED, MOM, BMOM, WD, KEEP, P, 2>), g, dim3(cfg.block), lds, s, t.start,
-                          t.stop, 0, a);
+    hipExtLaunchKernelGGL((task_barrier_kernel<R, MIXED, MOM, BMOM, WD, KEEP, P, false, 2>), g, dim3(cfg.block), lds, s,
+                          t.start, t.stop, 0, a);
   else if (cfg.unroll == 1)
-    hipExtLaunchKernelGGL((task_barrier_kernel<R, MIXED, MOM, BMOM, WD, KEEP, P, 1>), g, dim3(cfg.block), lds, s, t.start,
-                          t.stop, 0, a);
+    hipExtLaunchKernelGGL((task_barrier_kernel<R, MIXED, MOM, BMOM, WD, KEEP, P, false, 1>), g, dim3(cfg.block), lds, s,
+                          t.start, t.stop, 0, a);
   else
     return hipErrorInvalidValue;
   return hipGetLastError();

@@ -2,7 +2,8 @@
 the SMA step and the replica optimiser step over device buffers the caller
 owns, for a Crossbow build that keeps its own model manager and replaces only
 ``crossbowSynchronisationSMA`` (clib-multigpu/synch/sma.c:233-248) and
-``crossbowKernelOptimiserSMA`` (kernels/optimisers/sma.cu:3-100), and in the
+``crossbowKernelOptimiserSMA`` (kernels/optimisers/sma.cu:3-100), or with
+tau = 1 both in one launch (``SmaPlan.step_and_optimise``), and in the
 same way the synchronous-SGD, elastic-averaging (synch/synchronouseamsgd.c)
 and Polyak-Ruppert (synch/polyakruppert.c) barriers.
 
@@ -75,6 +76,29 @@ class SmaPlan:
             _ints(dev), _ptrs([r[1] for r in replicas]), _ptrs([r[2] for r in replicas]),
             _ints([r[3] for r in replicas]), _ints([r[4] for r in replicas]), ctypes.c_float(alpha),
             ctypes.c_float(momentum), first), "cbx_sma_plan_step")
+
+    def step_and_optimise(self, streams: Sequence[int], z: Sequence[int], last: Optional[Sequence[Optional[int]]],
+                          replicas: Sequence[Tuple[int, int, Optional[int], Optional[int], Optional[int], int, int, int,
+                                                   float]],
+                          alpha: float, momentum: float, replica_momentum: float, weight_decay: float,
+                          first: int = 0, flags: int = 0) -> int:
+        """The stepping replicas' task steps and the SMA step in one launch
+        (``cbx_sma_plan_step_and_optimise``; one device, one rank).
+        ``replicas[id]`` = (device index, w, s, g, rlast, locked, copy, step,
+        learning_rate): ``step`` != 0 means the replica's gradient ``g`` is
+        applied first, at ``learning_rate`` (positive), with ``rlast`` its
+        momentum buffer (None without replica momentum).  ``flags`` is 0 or
+        ``STEP_DISCARD_TASK_OUTPUTS``, under which a stepping replica's ``s``
+        may be None.  The caller orders ``streams[0]`` behind the gradients.
+        Returns 1 when Phase D ran."""
+        rate = (ctypes.c_float * max(1, len(replicas)))(*[float(r[8]) for r in replicas])
+        return _raise(self.lib, self.lib.cbx_sma_plan_step_and_optimise(
+            self._p, _ptrs(streams), _ptrs(z), _ptrs(last) if last is not None else None, len(replicas),
+            _ints([r[0] for r in replicas]), _ptrs([r[1] for r in replicas]), _ptrs([r[2] for r in replicas]),
+            _ptrs([r[3] for r in replicas]), _ptrs([r[4] for r in replicas]), _ints([r[5] for r in replicas]),
+            _ints([r[6] for r in replicas]), _ints([r[7] for r in replicas]), rate, ctypes.c_float(alpha),
+            ctypes.c_float(momentum), ctypes.c_float(replica_momentum), ctypes.c_float(weight_decay), first,
+            ctypes.c_uint(flags)), "cbx_sma_plan_step_and_optimise")
 
     def ssgd_step(self, streams: Sequence[int], z: Sequence[int], last: Optional[Sequence[Optional[int]]],
                   acc: Sequence[int], replicas: Sequence[Tuple[int, int, int]], momentum: float, wpc: int,

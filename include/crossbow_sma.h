@@ -806,6 +806,7 @@ int cbx_bench_copy (cbx_context *ctx, size_t bytes, int iters, float *gbps);
  *       -> cbx_sma_plan_step
  *   crossbowKernelOptimiserSMA (kernels/optimisers/sma.cu:3-100)
  *       -> cbx_sma_optimise_buffers
+ * (or, with tau = 1, both in one launch: cbx_sma_plan_step_and_optimise)
  * and, further down, the synchronous-SGD pair (cbx_ssgd_plan_step,
  * cbx_ssgd_accumulate_buffers), the elastic-averaging barrier
  * (cbx_ea_plan_step) and the Polyak-Ruppert barrier (cbx_pr_plan_step)
@@ -832,7 +833,8 @@ int cbx_sma_plan_free (cbx_sma_plan *plan);
 int cbx_sma_plan_set_buckets (cbx_sma_plan *plan, int buckets);
 /* Measurement aid for a one-rank plan (scripts/bench_averaging_seam.py):
  * with `on`, the fused launch of every step (cbx_sma_plan_step,
- * cbx_ea_plan_step, cbx_pr_plan_step) stamps its own start and stop, as the
+ * cbx_sma_plan_step_and_optimise, cbx_ea_plan_step, cbx_pr_plan_step) stamps
+ * its own start and stop, as the
  * context's cbx_set_timing does, into a ring of the last 256 steps; no
  * marker packet is added to the caller's stream.  Switching it (on or off)
  * empties the ring.  cbx_sma_plan_timing_history waits for the last of them
@@ -871,6 +873,65 @@ int cbx_sma_plan_timing_history (cbx_sma_plan *plan, float *ms, int count);
 int cbx_sma_plan_step (cbx_sma_plan *plan, void *const *streams, float *const *z, float *const *last,
                        int nreplicas, const int *replica_device, float *const *w, const float *const *s,
                        const int *locked, const int *copy, float alpha, float momentum, int first);
+/* The stepping replicas' task steps and the SMA step above in ONE launch over
+ * the caller's buffers (one device, one rank): what cbx_step_and_synchronise
+ * is to a context, for a tau = 1 build that replaces the pair
+ * crossbowKernelOptimiserSMA + crossbowSynchronisationSMA.  It moves
+ * (28R + 16) n bytes, or (20R + 16) n with the discard flag, where the two
+ * calls move (40R + 16) n.  Arguments named as for cbx_sma_plan_step mean
+ * the same; for replica id:
+ *     g[id]               replicas[id]->gradient->dev
+ *     rlast[id]           replicas[id]->last->dev (used iff replica_momentum > 0;
+ *                         otherwise `rlast` itself may be NULL)
+ *     step[id]            != 0: the replica holds a gradient that has not been
+ *                         applied and takes its task step in this call; 0: it
+ *                         joins the barrier with its s and w as they are
+ *     learning_rate[id]   crossbowSolverConfGetLearningRate (conf, task) of a
+ *                         stepping replica, positive, as cbx_sma_optimise_buffers
+ *                         takes it; read only where step[id] != 0.  The caller
+ *                         has made that query already, so the _copy flag it may
+ *                         raise is in copy[]
+ *   momentum          the base model's, as for cbx_sma_plan_step
+ *   replica_momentum, weight_decay   the stepping replicas' conf values, one
+ *                     pair for all of them
+ *   flags             0 or CBX_STEP_DISCARD_TASK_OUTPUTS
+ * The contract.  With flags == 0 every buffer (z, the base `last`, every w,
+ * rlast, s and g) is left bit for bit as after
+ *   cbx_sma_optimise_buffers (streams[0], w[id], g[id], rlast[id], s[id],
+ *       elements, learning_rate[id], replica_momentum, weight_decay)
+ *                                 for every id with step[id] != 0, in id order,
+ *   cbx_sma_plan_step (plan, streams, z, last, nreplicas, replica_device, w, s,
+ *       locked, copy, alpha, momentum, first).
+ * With CBX_STEP_DISCARD_TASK_OUTPUTS, s[id] and g[id] of the stepping replicas
+ * are not written at all (s[id] may then be NULL); the caller makes the promise
+ * stated at cbx_step_and_synchronise.  Returns 1 when Phase D ran (every
+ * participating w equals the new z; rlast, and s and g when kept, hold the
+ * step's values all the same), 0 when not.
+ * One launch on streams[0], asynchronous.  The plan adds no waits of its own:
+ * the caller orders streams[0] behind whatever produced each stepping
+ * replica's g (an event wait, as sma.c:63 waits on its events).  With
+ * cbx_sma_plan_set_timing on, the launch stamps itself into the plan's ring.
+ * Everything is checked before the launch: a refused call writes nothing, and
+ * cbx_last_error names the cause.  CBX_ERR_INVALID: a NULL plan, streams, z, or
+ * (nreplicas > 0) replica_device, w, s, g, locked, copy, step or
+ * learning_rate; `last` NULL with momentum > 0, `rlast` NULL with
+ * replica_momentum > 0 and a stepping replica; an unknown flag bit; `first`
+ * out of range; a stepping replica that is not locked or is below `first`; a
+ * participating replica on a device other than 0, with a NULL w[id], with a
+ * NULL s[id] (unless it steps under the discard flag) or a buffer that is not
+ * 16-byte aligned; a stepping replica with a NULL g[id], or with a NULL
+ * rlast[id] when replica_momentum > 0.  CBX_ERR_UNSUPPORTED: a plan with more
+ * than one device or a communicator of more than one rank (kernel A is not
+ * fused); more than 64 participating replicas.  Nesterov momentum stays the
+ * caller's err() (sma.cu:46-48): the call has no method argument.         */
+int cbx_sma_plan_step_and_optimise (cbx_sma_plan *plan, void *const *streams,
+                                    float *const *z, float *const *last,
+                                    int nreplicas, const int *replica_device,
+                                    float *const *w, float *const *s, float *const *g, float *const *rlast,
+                                    const int *locked, const int *copy, const int *step,
+                                    const float *learning_rate,
+                                    float alpha, float momentum, float replica_momentum, float weight_decay,
+                                    int first, unsigned flags);
 /* The statistics reduction of cbx_model_stats over caller-owned buffers of
  * exactly the plan's `elements` floats on the plan's device k (where a
  * Crossbow build would checksum, databuffer.c:141-162): `ref` against
