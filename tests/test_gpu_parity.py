@@ -606,6 +606,9 @@ def test_golden_fixtures_on_gpu():
             for k in range(st.size):
                 assert_bitexact(got.w[k], case["w_out"][k], f"{case['name']} w[{k}]")
             assert_bitexact(got.z[0], case["z_out"][0], f"{case['name']} z")
+            if st.momentum > 0:
+                assert case["last_out"] is not None, f"{case['name']}: the fixture carries no base last"
+                assert_bitexact(got.last[0], case["last_out"][0], f"{case['name']} last")
         finally:
             g.free()
 
