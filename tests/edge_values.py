@@ -19,11 +19,17 @@ ISA-defined); everywhere else the 32 bits are equal.  Buffers that are copies
 in the reference are compared with ``tests.helpers.assert_bitexact``, NaN
 payloads included.
 
+The last section serves the two reductions (the gradient norm and the model
+statistics; tests/test_reduction_edges.py, tests/test_gpu_reduction_edges.py):
+whole-buffer regimes whose fp64 sums are exact in any order, a wide catalogue
+over the pair (x, ref), and an exact reference in Python integers.
+
 Test infrastructure only; not a conftest.
 """
 from __future__ import annotations
 
 import itertools
+from fractions import Fraction
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -36,6 +42,9 @@ assert N < 16_384 and N % 4 != 0
 
 ALPHA = 0.1
 LR = 0.05  # the base learning rate; the kernels see -rate
+WD = 5e-4
+# (replica momentum, weight decay) of the task steps: momentum + wd, plain, wd only, momentum only
+OPT_CONFIGS = {"mom-wd": (0.9, WD), "plain": (0.0, 0.0), "wd-only": (0.0, WD), "mom-only": (0.9, 0.0)}
 
 
 def b32(x) -> int:
@@ -361,6 +370,12 @@ def is_subnormal(a: np.ndarray) -> np.ndarray:
     return ((b & 0x7F800000) == 0) & ((b & 0x007FFFFF) != 0)
 
 
+def flush(a: np.ndarray) -> None:
+    """What a flush-to-zero device makes of ``a``, in place: every subnormal a zero of its sign."""
+    b = a.view(np.uint32)
+    b[is_subnormal(a)] &= np.uint32(SIGN)
+
+
 def census(arrays: Sequence[np.ndarray]) -> Dict[str, int]:
     """How many +0, -0, subnormals, +inf, -inf and NaNs the arrays hold."""
     out = dict.fromkeys(("+0", "-0", "subnormal", "+inf", "-inf", "nan"), 0)
@@ -405,18 +420,18 @@ def averaging_case(R: int, momentum: float, alpha: float = ALPHA):
 
 
 def optimiser_case(momentum: float, wd: float, rate: float = -LR, seed: int = 300, extra: Sequence[str] = (),
-                   last: bool = True):
+                   last: bool = True, n: int = N):
     """w, g, last (None without momentum) and one array per name in ``extra``
-    with the task step's catalogue written in, and an s of ordinary data that
-    the step overwrites.  Returns (arrays by name, labels)."""
+    of ``n`` floats with the task step's catalogue written in, and an s of
+    ordinary data that the step overwrites.  Returns (arrays by name, labels)."""
     from oracle import oracle as O
-    a = {"w": O.fill_normal(N, seed, 0.05), "g": O.fill_normal(N, seed + 1, 0.01)}
+    a = {"w": O.fill_normal(n, seed, 0.05), "g": O.fill_normal(n, seed + 1, 0.01)}
     if momentum > 0 and last:
-        a["last"] = O.fill_normal(N, seed + 2, 0.001)
+        a["last"] = O.fill_normal(n, seed + 2, 0.001)
     for k, x in enumerate(extra):
-        a[x] = O.fill_normal(N, seed + 4 + k, 0.05 if x == "z" else 0.001)
-    labels = apply(a, optimiser_scenarios(rate, momentum, wd, last="last" if "last" in a else None, extra=extra))
-    a["s"] = O.fill_normal(N, seed + 3, 7.0)
+        a[x] = O.fill_normal(n, seed + 4 + k, 0.05 if x == "z" else 0.001)
+    labels = apply(a, optimiser_scenarios(rate, momentum, wd, last="last" if "last" in a else None, extra=extra), n)
+    a["s"] = O.fill_normal(n, seed + 3, 7.0)
     a.setdefault("last", None)
     return a, labels
 
@@ -440,3 +455,208 @@ def fused_case(data, rmom: float, wd: float, rates: Sequence[float], steps: Sequ
 
 def nan_fraction(a: np.ndarray) -> float:
     return float(np.mean(np.isnan(np.ascontiguousarray(a, dtype=np.float32))))
+
+
+# ---- the reductions: the gradient norm and the model statistics ---------------------------
+# Two whole 4,096-float tiles of the norm pass (its unrolled path) and a partial
+# one of 225 float4s and 3 floats; a 903-float tail on the seam's TAIL workgroups.
+N_RED = 2 * 4096 + 903
+assert N_RED % 4 == 3 and N_RED % 1024 == TAIL and (N_RED % 4096) // 4 == 225
+
+ULP = Fraction(1, 2 ** 149)  # every finite float is an integer multiple of it
+
+
+def to_ints(a: np.ndarray) -> List[Optional[int]]:
+    """Every finite float as the integer k of x = k * 2^-149; None for a
+    non-finite one."""
+    out = []
+    for b in bits(a).tolist():
+        e, m = (b >> 23) & 0xFF, b & 0x7FFFFF
+        if e == 0xFF:
+            out.append(None)
+            continue
+        k = m if e == 0 else (m | 0x800000) << (e - 1)
+        out.append(-k if b & SIGN else k)
+    return out
+
+
+def exact_stats(x: Sequence[Optional[int]], xbits: np.ndarray, ref: Optional[Sequence[Optional[int]]] = None):
+    """The statistics of ``cbx_buffer_stats`` over the integers of ``to_ints``,
+    in exact arithmetic: sum, sum_sq, dist_sq and the sums of their terms'
+    magnitudes as Fractions; nonfinite; the bits of max_abs.  A non-finite x
+    only counts; a finite x beside a non-finite reference adds to everything
+    but dist_sq (against None: x is the reference, dist_sq is 0)."""
+    s = sa = q = d = 0
+    nf = 0
+    for i, k in enumerate(x):
+        if k is None:
+            nf += 1
+            continue
+        s += k
+        sa += abs(k)
+        q += k * k
+        if ref is not None and ref[i] is not None:
+            d += (k - ref[i]) ** 2
+    b = xbits & np.uint32(0x7FFFFFFF)
+    b = b[b < PINF]
+    return {"sum": s * ULP, "sum_abs": sa * ULP, "sum_sq": q * ULP * ULP, "dist_sq": d * ULP * ULP, "nonfinite": nf,
+            "max_abs": int(b.max()) if b.size else 0, "m": len(x)}
+
+
+EPS53 = Fraction(1, 2 ** 53)
+
+
+def assert_stats_record(rec, want, exact: bool, what: str) -> None:
+    """One ``cbx_buffer_stats`` record against ``exact_stats``: the counts and
+    the bits of max_abs always equal; the sums equal (``exact``) or within the
+    reordering bound of an fp64 sum of m exact terms, 2 m 2^-53 sum |term|."""
+    assert int(rec["nonfinite"]) == want["nonfinite"], (what, int(rec["nonfinite"]), want["nonfinite"])
+    got_max = int(np.array([rec["max_abs"]], np.float32).view(np.uint32)[0])
+    assert got_max == want["max_abs"], f"{what}: max_abs {got_max:#010x}, want {want['max_abs']:#010x}"
+    assert int(rec["reserved"]) == 0, what
+    for field, mag in (("sum", "sum_abs"), ("sum_sq", "sum_sq"), ("dist_sq", "dist_sq")):
+        v = float(rec[field])
+        assert np.isfinite(v), (what, field, v)
+        if exact:
+            assert Fraction(v) == want[field], f"{what}: {field} = {v!r}, want {float(want[field])!r} exactly"
+        else:
+            err, bound = abs(Fraction(v) - want[field]), 2 * want["m"] * EPS53 * want[mag]
+            assert err <= bound, f"{what}: {field} = {v!r} is {float(err)!r} off, bound {float(bound)!r}"
+
+
+class Regime:
+    """Whole buffers of one kind of value: ``make(n, seed)`` gives an fp32 array."""
+
+    def __init__(self, name, make, exact):
+        self.name, self.make, self.exact = name, make, exact
+
+    def __repr__(self):
+        return self.name
+
+
+K_MAX = 2 ** 18
+
+
+def _scaled_integers(shift):
+    def make(n, seed):
+        rng = np.random.default_rng(7000 + seed)
+        k = rng.integers(-K_MAX, K_MAX + 1, n)
+        k[k == 0] = 1
+        k[:2] = (K_MAX, -K_MAX)  # the bound of the exactness argument is reached
+        return np.ldexp(k.astype(np.float64), shift).astype(np.float32)
+    return make
+
+
+def _uniform_power(e):
+    def make(n, seed):
+        rng = np.random.default_rng(7100 + seed)
+        sign = np.where(rng.integers(0, 2, n) == 1, -1.0, 1.0)
+        return np.ldexp(sign, e).astype(np.float32)
+    return make
+
+
+def _range_end(n, seed):
+    rng = np.random.default_rng(7200 + seed)
+    b = (rng.integers(0, 2, n).astype(np.uint32) << np.uint32(31)) | \
+        (rng.integers(253, 255, n).astype(np.uint32) << np.uint32(23)) | rng.integers(0, 2 ** 23, n).astype(np.uint32)
+    b[:2] = (FLT_MAX, FLT_MAX | SIGN)
+    return b.view(np.float32)
+
+
+# x = k 2^-149 (subnormals: their squares underflow in fp32) and k 2^104 (their
+# squares overflow in fp32), |k| <= 2^18: n k^2 and n (k - k_ref)^2 stay below
+# 2^53, so the three sums are exact in fp64 in any order.  The same for +-2^e.
+REGIMES = (Regime("subnormal", _scaled_integers(-149), True), Regime("mid-range", _scaled_integers(104), True),
+           Regime("min-sub", _uniform_power(-149), True), Regime("FLT_MIN", _uniform_power(-126), True),
+           Regime("2^127", _uniform_power(127), True), Regime("range-end", _range_end, False))
+
+
+def reduction_catalogue() -> List[Scenario]:
+    """The wide catalogue of the reductions over the pair (x, ref): every entry
+    of SWEEP in each, the signed zeros, and the pairs that the masks of
+    ``cbx_buffer_stats`` tell apart.  In groups of three that a run of 3-float
+    variables keeps together: the huge values share no variable with a mask
+    pair, so that pair's record has a bound with teeth."""
+    h, t = b32(0.75), b32(-0.3125)
+    out = sweep(["x"]) + [("x=-FLT_MAX again", {"x": FLT_MAX | SIGN}), ("x=0.75", {"x": h})]
+    out += sweep(["ref"]) + [("ref=-0.3125", {"ref": t}), ("ref=0.75", {"ref": h})]
+    out += signed_zeros(["x", "ref"]) + [("x=ref=-0", {"x": NZERO, "ref": NZERO}), ("x=-0 again", {"x": NZERO})]
+    out += [("x=+inf beside a finite ref", {"x": PINF, "ref": h}), ("x finite beside ref=+inf", {"x": h, "ref": PINF}),
+            ("x=snan beside a finite ref", {"x": SNAN, "ref": t}),
+            ("x finite beside ref=payload-nan", {"x": t, "ref": PAYLOAD_NAN}),
+            ("x finite beside ref=-inf", {"x": t, "ref": NINF}), ("x == ref", {"x": h, "ref": h}),
+            ("x=+min-sub ref=-min-sub", {"x": MIN_SUB, "ref": MIN_SUB | SIGN}),
+            ("x=-min-sub ref=+min-sub", {"x": MIN_SUB | SIGN, "ref": MIN_SUB}),
+            ("x == ref, both max-sub", {"x": MAX_SUB, "ref": MAX_SUB}),
+            ("x=+FLT_MAX ref=-FLT_MAX", {"x": FLT_MAX, "ref": FLT_MAX | SIGN}),
+            ("x=-FLT_MAX ref=+FLT_MAX", {"x": FLT_MAX | SIGN, "ref": FLT_MAX}),
+            ("x == ref, both FLT_MAX", {"x": FLT_MAX, "ref": FLT_MAX}),
+            ("every x of a variable NaN: 1", {"x": QNAN}), ("every x of a variable NaN: 2", {"x": PAYLOAD_NAN}),
+            ("every x of a variable NaN: 3", {"x": SNAN}),
+            ("every x of a variable -0: 1", {"x": NZERO}), ("every x of a variable -0: 2", {"x": NZERO, "ref": NZERO}),
+            ("every x of a variable -0: 3", {"x": NZERO, "ref": PINF})]
+    assert len(out) % 3 == 0
+    return out
+
+
+def stats_variables(L: int, n: int = N_RED) -> Tuple[Tuple[int, ...], int, int]:
+    """The statistics tests' variable list for catalogues of up to ``L``
+    entries, and where the two copies start: one float (every later variable
+    starts off a float4), a large variable that holds the first copy on the
+    aligned float4 path, ceil(L/3) variables of 3 floats whose every float
+    takes the scalar path and which hold the second copy, and the remainder."""
+    run = -(-L // 3)
+    big = 4600
+    variables = (1, big) + (3,) * run + (n - 1 - big - 3 * run,)
+    assert variables[-1] > 0 and sum(variables) == n
+    second = 1 + big
+    first = 8
+    while (second - first) % 4 != 1:
+        first += 1
+    return variables, first, second
+
+
+def stats_pieces(variables: Sequence[int], tile: int = 4096) -> List[Tuple[int, int, int, bool]]:
+    """The piece table of crossbow_amd/csrc/stats_plan.h restated: (lo, hi,
+    variable, aligned) in offset order."""
+    out, lo = [], 0
+    for v, count in enumerate(variables):
+        hi = lo + count
+        a = lo
+        while a < hi:
+            b = min((a // tile + 1) * tile, hi)
+            a4, b4 = (a + 3) // 4 * 4, b // 4 * 4
+            cut = [(a, a4, False), (a4, b4, True), (b4, b, False)] if a4 < b4 else [(a, b, False)]
+            out += [(x, y, v, al) for x, y, al in cut if x < y]
+            a = b
+        lo = hi
+    return out
+
+
+def apply_at(arrays: Dict[str, np.ndarray], scen: Sequence[Scenario], starts: Sequence[int]) -> List[Optional[str]]:
+    """``apply`` with the copies' start offsets given (the statistics tests'
+    second copy lies in the scalar run, not at the buffer's end)."""
+    n = next(iter(arrays.values())).size
+    labels: List[Optional[str]] = [None] * n
+    views = {}
+    for name, a in arrays.items():
+        assert a.dtype == np.float32 and a.size == n and a.flags.c_contiguous, name
+        views[name] = a.view(np.uint32)
+    for start in starts:
+        assert 0 <= start and start + len(scen) <= n
+        for k, (label, vals) in enumerate(scen):
+            assert labels[start + k] is None, "the copies overlap"
+            for name, v in vals.items():
+                views[name][start + k] = v
+            labels[start + k] = label
+    return labels
+
+
+def finite_gradient(a: Dict[str, Optional[np.ndarray]], seed: int = 900) -> Dict[str, Optional[np.ndarray]]:
+    """The finite-g form of an ``optimiser_case``: every non-finite g is replaced
+    by ordinary data; w and last keep theirs."""
+    from oracle import oracle as O
+    out = {k: (v.copy() if v is not None else None) for k, v in a.items()}
+    bad = ~np.isfinite(out["g"])
+    out["g"][bad] = O.fill_normal(out["g"].size, seed, 0.01)[bad]
+    return out

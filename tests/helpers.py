@@ -68,3 +68,28 @@ def compare_states(got: O.SmaState, want: O.SmaState, exact: bool = True, rtol=1
                 assert_bitexact(a, b, f"{name}[{k}]")
             else:
                 np.testing.assert_allclose(a, b, rtol=rtol, atol=atol, err_msg=f"{name}[{k}]")
+
+
+GUARD = 1028 + 60  # floats behind every caller-owned buffer: more than a kPadFloat4's worth of pad plus a float4
+
+
+class Guarded:
+    """One device allocation: n floats of data, then GUARD sentinel floats."""
+
+    def __init__(self, arr, tag):
+        import torch
+        self.n = arr.size
+        bits = np.arange(GUARD, dtype=np.uint32) * np.uint32(2654435761) + np.uint32(0x7FC00000 + tag)
+        self.sentinel = bits.view(np.float32)  # every kind of value, NaNs among them
+        host = np.concatenate([arr.astype(np.float32, copy=False), self.sentinel])
+        self.t = torch.from_numpy(host.copy()).to("cuda:0")
+        assert self.t.data_ptr() % 16 == 0
+
+    @property
+    def ptr(self):
+        return self.t.data_ptr()
+
+    def check(self, want, name):
+        host = self.t.cpu().numpy()
+        assert_bitexact(host[:self.n], want, name)
+        assert_bitexact(host[self.n:], self.sentinel, f"the floats behind {name}")

@@ -32,9 +32,8 @@ from tests.test_gpu_seam_step_and_optimise import DISCARD, Data, Guarded
 
 pytestmark = pytest.mark.gpu
 
-N, ALPHA, LR, WD = E.N, E.ALPHA, E.LR, 5e-4
-# (replica momentum, weight decay): momentum + wd, plain, wd only, momentum only
-OPT_CONFIGS = {"mom-wd": (0.9, WD), "plain": (0.0, 0.0), "wd-only": (0.0, WD), "mom-only": (0.9, 0.0)}
+N, ALPHA, LR, WD = E.N, E.ALPHA, E.LR, E.WD
+OPT_CONFIGS = E.OPT_CONFIGS
 
 
 def _has(a, pattern):

@@ -26,36 +26,7 @@ ZERO = {"sum_sq": 0.0, "nonfinite": 0, "scale": 0.0, "flags": 0, "steps": 0, "cl
 sweep = pytest.mark.parametrize("n,momentum,wd", [(n, m, wd) for n in SHAPES for m in (0.0, 0.9) for wd in (0.0, 5e-4)])
 
 
-def _gpu(n, momentum, wd, replicas=1, update_type=7, variables=None, mults=None, alpha=0.1):
-    from crossbow_amd import TheGPU
-    variables = variables or [n]
-    g = TheGPU()
-    g.init([0])
-    g.setModel(len(variables), 4 * n)
-    for v, count in enumerate(variables):
-        g.setModelVariable(v, 1, [count], 4 * count)
-        if mults is not None:
-            g.setModelVariableLearningRateMultiplier(v, 1, mults[v])
-    g.setUpdateModelType(update_type)
-    g.setEamsgdAlpha(alpha)
-    g.setMomentum(momentum, 0)
-    g.setWeightDecay(wd)
-    g.setLearningRateDecayPolicyFixed(C.LR)
-    g.setModelManager(replicas, 0)
-    return g
-
-
-def _put(gpu, i, bufs):
-    from crossbow_amd import BUF_DATA, BUF_DIFF, BUF_GRADIENT, BUF_LAST
-    for kind, a in zip((BUF_DATA, BUF_GRADIENT, BUF_LAST, BUF_DIFF), bufs):
-        if a is not None:
-            gpu.replica_write(i, kind, a)
-
-
-def _get(gpu, i, momentum):
-    from crossbow_amd import BUF_DATA, BUF_DIFF, BUF_GRADIENT, BUF_LAST
-    return [gpu.replica_read(i, kind) if (kind != BUF_LAST or momentum > 0) else None
-            for kind in (BUF_DATA, BUF_GRADIENT, BUF_LAST, BUF_DIFF)]
+_gpu, _put, _get = C.context, C.put, C.get
 
 
 def _check(gpu, i, bufs, what="", nans=False):

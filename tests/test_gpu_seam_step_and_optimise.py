@@ -19,13 +19,12 @@ import pytest
 
 from oracle import oracle as O
 from tests import multidev_common as C
-from tests.helpers import assert_bitexact
+from tests.helpers import GUARD, Guarded, assert_bitexact  # noqa: F401 (Guarded: other test files take it from here)
 
 pytestmark = pytest.mark.gpu
 
 ALPHA = 0.1
 DISCARD = 1  # CBX_STEP_DISCARD_TASK_OUTPUTS
-GUARD = 1028 + 60  # floats behind every buffer: more than a kPadFloat4's worth of pad plus a float4
 # (replica momentum, weight decay, base momentum); the last has base and replica momentum that differ
 CONFIGS = {"mom-wd": (0.9, 5e-4, 0.9), "plain": (0.0, 0.0, 0.0), "base-mom-only": (0.0, 5e-4, 0.9)}
 
@@ -57,28 +56,6 @@ class Data:
         for i, (s, g) in kept.items():
             st.s[i], self.g[i] = s, g
         return 1 if copies > 0 else 0
-
-
-class Guarded:
-    """One device allocation: n floats of data, then GUARD sentinel floats."""
-
-    def __init__(self, arr, tag):
-        import torch
-        self.n = arr.size
-        bits = np.arange(GUARD, dtype=np.uint32) * np.uint32(2654435761) + np.uint32(0x7FC00000 + tag)
-        self.sentinel = bits.view(np.float32)  # every kind of value, NaNs among them
-        host = np.concatenate([arr.astype(np.float32, copy=False), self.sentinel])
-        self.t = torch.from_numpy(host.copy()).to("cuda:0")
-        assert self.t.data_ptr() % 16 == 0
-
-    @property
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def check(self, want, name):
-        host = self.t.cpu().numpy()
-        assert_bitexact(host[:self.n], want, name)
-        assert_bitexact(host[self.n:], self.sentinel, f"the floats behind {name}")
 
 
 class Buffers:
