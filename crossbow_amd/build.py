@@ -37,7 +37,7 @@ def _hipcc() -> str:
 SOURCES = ("context.hip", "sync_steps.hip", "sma_kernels.hip", "averaging_kernels.hip", "sma_seam.hip",
            "stats_kernels.hip", "variable_rate_kernels.hip", "clip_kernels.hip", "task_barrier_kernels.hip")
 HEADERS = ("context_internal.h", "sma_internal.h", "stream_helpers.h", "stats_internal.h", "stats_plan.h",
-           "optimise_plan.h", "clip_internal.h")
+           "optimise_plan.h", "clip_internal.h", "bucket_pipeline.h")
 
 
 def _sources():

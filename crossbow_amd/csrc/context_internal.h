@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "../../include/crossbow_sma.h"
+#include "bucket_pipeline.h"
 #include "clip_internal.h"
 #include "sma_internal.h"
 #include "stats_internal.h"
@@ -669,8 +670,7 @@ constexpr size_t kAlign = 2u << 20;
 // element index do not all start on the same 2 MiB boundary (measured +1-2 %
 // on the fused kernel, scripts/membench.hip, profiles/r01).
 constexpr size_t kSlotStagger = 4096;
-// Buckets of the G > 1 pipeline when cbx_set_bucket_elements was not called.
-constexpr int64_t kDefaultBuckets = 8;
+static_assert(kBucketPad4 == cbx::kPadFloat4, "bucket starts are whole kernel trips");
 
 inline size_t slot_index_base(int kind) {
   switch (kind) {
@@ -1074,8 +1074,61 @@ int bn_average(std::vector<BnDevice> &devs, int layers, const int *elements, flo
 int grow_device_buffer(void **p, size_t *have, size_t need);
 
 // ---- the barrier steps (sync_steps.hip) ------------------------------------
-// The same arguments over float4s [start4, start4 + len4) of every buffer.
-cbx::SmaArgs offset_args(const cbx::SmaArgs &a, int64_t start4, int64_t len4);
+// What a lane of the bucket pipeline (bucket_pipeline.h) is in either door: a
+// device, the step's stream, the stream its all-reduces run on beside it, the
+// per-bucket events between the two, and the all-reduce of the n floats of
+// `src` into `dst`, whose last bucket extends to n.  `ctrl`: the control block
+// in front of both buffers rides bucket 0 (common.c:14-54).  A step adds its
+// launches.
+struct PipelineLane {
+  int hip_id, num_cus;
+  hipStream_t stream, comm_stream;
+  const std::vector<hipEvent_t> &ev_a, &ev_r;
+  ncclComm_t comm;
+  float *src, *dst;
+  int64_t n;
+  bool ctrl;
+  int select() {
+    HIP_TRY(hipSetDevice(hip_id));
+    return CBX_OK;
+  }
+  int record_a(int64_t b) {
+    HIP_TRY(hipEventRecord(ev_a[b], stream));
+    return CBX_OK;
+  }
+  int wait_a(int64_t b) {
+    HIP_TRY(hipStreamWaitEvent(comm_stream, ev_a[b], 0));
+    return CBX_OK;
+  }
+  int record_r(int64_t b) {
+    HIP_TRY(hipEventRecord(ev_r[b], comm_stream));
+    return CBX_OK;
+  }
+  int wait_r(int64_t b) {
+    HIP_TRY(hipStreamWaitEvent(stream, ev_r[b], 0));
+    return CBX_OK;
+  }
+  int all_reduce(const Bucket &b, bool on_comm) {
+    const int64_t lo = b.start4 * 4, hi = b.last ? n : (b.start4 + b.len4) * 4;
+    const int64_t head = ctrl && b.first ? cbx::kCtrlFloats : 0;
+    NCCL_TRY(ncclAllReduce(src + lo - head, dst + lo - head, (size_t)(hi - lo + head), ncclFloat, ncclSum, comm,
+                           on_comm ? comm_stream : stream));
+    return CBX_OK;
+  }
+  cbx::LaunchConfig on_device(cbx::LaunchConfig cfg) const {
+    cfg.num_cus = num_cus;
+    return cfg;
+  }
+};
+// The bracket around the all-reduces of one bucket.
+inline int group_begin() {
+  NCCL_TRY(ncclGroupStart());
+  return CBX_OK;
+}
+inline int group_end() {
+  NCCL_TRY(ncclGroupEnd());
+  return CBX_OK;
+}
 // SMA (synch/sma.c:13-231): fused at G = 1; kernel A / collective / kernel B
 // per bucket at G > 1 (or forced); the peer-read form.
 int sma_step(cbx_context *c, int first);

@@ -27,6 +27,10 @@
 // in the reference, sma.c:66,82) with the 256-byte control block that carries
 // the Phase-D request count through the all-reduce, and -- unless the caller
 // hands over its own (executioncontext.c:185-201) -- the RCCL communicators.
+//
+// With several ranks the SMA, averaging and S-SGD steps are bucketed: each
+// supplies its lanes (PlanLane) and bucket_pipeline.h holds the order in
+// which they are enqueued, its diagrams, and the bucket geometry.
 #include "context_internal.h"
 #include "optimise_plan.h"
 
@@ -133,16 +137,91 @@ int ensure_pipeline(cbx_sma_plan *p, int64_t nb) {
   return CBX_OK;
 }
 
+// A lane of a bucketed step over the caller's buffers (bucket_pipeline.h holds
+// the order and the diagrams): the plan's device k, the caller's stream, and
+// the all-reduce of `src` into the plan's D.  The tail rides the last bucket:
+// its launches take it (bucket_args) and its all-reduce extends to n.
+struct PlanLane : PipelineLane {
+  cbx_sma_plan *p;
+  PlanLane(cbx_sma_plan *plan, int k, void *const *streams, float *src, bool ctrl)
+      : PipelineLane{plan->devs[k].hip_id, plan->devs[k].num_cus, static_cast<hipStream_t>(streams[k]),
+                     plan->devs[k].comm_stream, plan->devs[k].ev_a, plan->devs[k].ev_r, plan->devs[k].comm, src,
+                     plan->devs[k].D_ctrl + cbx::kCtrlFloats, plan->n, ctrl},
+        p(plan) {}
+  template <class Args>
+  Args bucket_args(const Args &a, const Bucket &b) const {
+    const Args r = range_of(a, b.start4, b.len4);
+    return b.last ? with_tail(r, p->n4b, p->n, b.start4) : r;
+  }
+};
+
+struct SmaPlanLane : PlanLane {
+  const cbx::SmaArgs &args;
+  bool mom;
+  int launch_a(const Bucket &b) {
+    HIP_TRY(cbx::launch_sma_accumulate(bucket_args(args, b), b.first, on_device(p->cfg), stream));
+    return CBX_OK;
+  }
+  int launch_b(const Bucket &b) {
+    HIP_TRY(cbx::launch_sma_apply(bucket_args(args, b), mom, on_device(p->apply_cfg), stream));
+    return CBX_OK;
+  }
+};
+
+struct AveragingPlanLane : PlanLane {
+  const cbx::AvgArgs &args;
+  cbx::AvgModel model;
+  int launch_a(const Bucket &b) {
+    HIP_TRY(cbx::launch_averaging_accumulate(model, bucket_args(args, b), on_device(p->avg_cfg), stream));
+    return CBX_OK;
+  }
+  int launch_b(const Bucket &b) {
+    HIP_TRY(cbx::launch_averaging_apply(model, bucket_args(args, b), on_device(p->apply_cfg), stream));
+    return CBX_OK;
+  }
+};
+
+struct SsgdPlanLane : PlanLane {
+  const cbx::SsgdArgs &args;
+  int launch_k(const Bucket &b) {
+    HIP_TRY(cbx::launch_ssgd_apply(bucket_args(args, b), on_device(p->ssgd_apply_cfg), stream));
+    return CBX_OK;
+  }
+};
+
+// Per device: its locked replicas from `first` on, in id order (sma.c:69-73,
+// common.c:208).  Each one's device index and buffers are checked (`s` null:
+// the step takes no snapshots; `bad_buffers`: the step's refusal, with the
+// replica's id), its w is appended to its device's arguments, and `append`
+// adds what else the step keeps of replica `id` at slot a.nrep.
+template <class Args, class Append>
+int gather_replicas(std::vector<Args> &args, int first, int nreplicas, const int *replica_device, const int *locked,
+                    float *const *w, const float *const *s, const char *bad_buffers, Append append) {
+  const int G = (int)args.size();
+  for (int id = first; id < nreplicas; ++id) {
+    if (!locked[id]) continue;
+    const int k = replica_device[id];
+    if (k < 0 || k >= G) return fail(CBX_ERR_INVALID, "replica %d on device %d of %d", id, k, G);
+    if (!w[id] || !aligned16(w[id]) || (s && (!s[id] || !aligned16(s[id])))) return fail(CBX_ERR_INVALID, bad_buffers, id);
+    Args &a = args[k];
+    if (a.nrep >= cbx::kMaxReplicas)
+      return fail(CBX_ERR_UNSUPPORTED, "more than %d locked replicas on one device", cbx::kMaxReplicas);
+    a.w[a.nrep] = reinterpret_cast<cbx::v4f *>(w[id]);
+    append(a, id);
+    ++a.nrep;
+  }
+  return CBX_OK;
+}
+const char *const kBadReplicaBuffers = "replica %d: buffers must be non-null and 16-byte aligned";
+
 // The elastic-averaging (synch/synchronouseamsgd.c:5-101, :106-305) and
 // Polyak-Ruppert (synch/polyakruppert.c:5-138, :140-317) barriers over the
 // caller's buffers: the context's averaging_step (sync_steps.hip) with the
 // plan's scratch for acc / D.  One rank: the fused kernel.  Several: kernel A,
-// the all-reduce of acc into D, kernel B, bucketed as cbx_sma_plan_step is
-//   stream      : A(0) A(1) [wait r(0)] B(0) A(2) [wait r(1)] B(1) ...
-//   comm_stream : [wait a(0)] AR(0) [wait a(1)] AR(1) ...
-// with no control block; the tail rides the last bucket.  Everything is
-// validated before the first launch.  Returns the raised copy flags among the
-// locked replicas from `first` on (Polyak-Ruppert; 0 for elastic averaging).
+// the all-reduce of acc into D, kernel B, bucketed as cbx_sma_plan_step is,
+// with no control block.  Everything is validated before the first launch.
+// Returns the raised copy flags among the locked replicas from `first` on
+// (Polyak-Ruppert; 0 for elastic averaging).
 int averaging_plan_step(cbx_sma_plan *p, const char *what, bool polyak, void *const *streams, float *const *z,
                         float *const *last, int nreplicas, const int *replica_device, float *const *w,
                         const float *const *s, const int *locked, const int *copy, float alpha, int clock,
@@ -165,23 +244,17 @@ int averaging_plan_step(cbx_sma_plan *p, const char *what, bool polyak, void *co
       return fail(CBX_ERR_INVALID, "device %d: base buffers must be non-null and 16-byte aligned", k);
   }
   int copies = 0;
-  for (int id = first; id < nreplicas; ++id) {
-    if (!locked[id]) continue;
-    const int k = replica_device[id];
-    if (k < 0 || k >= G) return fail(CBX_ERR_INVALID, "replica %d on device %d of %d", id, k, G);
-    if (!w[id] || !aligned16(w[id]) || (snap && (!s[id] || !aligned16(s[id]))))
-      return fail(CBX_ERR_INVALID, "replica %d: buffers must be non-null and 16-byte aligned", id);
-    cbx::AvgArgs &a = args[k];
-    if (a.nrep >= cbx::kMaxReplicas)
-      return fail(CBX_ERR_UNSUPPORTED, "more than %d locked replicas on one device", cbx::kMaxReplicas);
-    if (snap) a.s[a.nrep] = reinterpret_cast<const cbx::v4f *>(s[id]);
-    a.w[a.nrep] = reinterpret_cast<cbx::v4f *>(w[id]);
-    if (polyak && copy[id]) {  // polyakruppert.c:126
-      a.copy_mask |= 1ull << a.nrep;
-      ++copies;
-    }
-    ++a.nrep;
-  }
+  TRY(gather_replicas(args, first, nreplicas, replica_device, locked, w, snap ? s : nullptr, kBadReplicaBuffers,
+                      [&](cbx::AvgArgs &a, int id) {
+                        if (snap) a.s[a.nrep] = reinterpret_cast<const cbx::v4f *>(s[id]);
+                        if (polyak && copy[id]) {  // polyakruppert.c:126
+                          a.copy_mask |= 1ull << a.nrep;
+                          ++copies;
+                        }
+                      }));
+  const BucketGrid grid = BucketGrid::by_count(p->n4b, p->buckets);
+  if (p->ranks > 1 && grid.nb > 1) TRY(ensure_pipeline(p, grid.nb));
+  std::vector<AveragingPlanLane> lanes;
   for (int k = 0; k < G; ++k) {
     auto &d = p->devs[k];
     cbx::AvgArgs &a = args[k];
@@ -189,95 +262,22 @@ int averaging_plan_step(cbx_sma_plan *p, const char *what, bool polyak, void *co
     a.last = polyak && last ? reinterpret_cast<cbx::v4f *>(last[k]) : nullptr;
     a.acc = reinterpret_cast<cbx::v4f *>(d.acc_ctrl + cbx::kCtrlFloats);
     a.D = reinterpret_cast<const cbx::v4f *>(d.D_ctrl + cbx::kCtrlFloats);
+    a.n4 = p->n4b;
     a.alpha = alpha;
     if (polyak) {
       a.scale = (float)(1.0 / (double)(float)nreplicas);      // polyakruppert.c:15
       a.running = (float)(1.0 / (double)(float)(clock + 1));  // :16
     }
+    lanes.push_back({PlanLane(p, k, streams, d.acc_ctrl + cbx::kCtrlFloats, false), a, model});
   }
-  // Bucket b of device k: `len4` float4s from `start4`, plus, on the launch
-  // that covers the buffers' end, the elements past the last whole chunk.
-  auto range = [&](const cbx::AvgArgs &a, int64_t start4, int64_t len4, bool tail) {
-    cbx::AvgArgs b = a;
-    for (int r = 0; r < a.nrep; ++r) {
-      if (a.s[r]) b.s[r] = a.s[r] + start4;
-      b.w[r] = a.w[r] + start4;
-    }
-    b.z = a.z + start4;
-    if (a.last) b.last = a.last + start4;
-    b.acc = a.acc + start4;
-    b.D = a.D + start4;
-    b.n4 = len4;
-    if (tail) {
-      b.tail_lo = (p->n4b - start4) * 4;
-      b.tail_hi = p->n - start4 * 4;
-    }
-    return b;
-  };
   if (p->ranks == 1) {
-    auto &d = p->devs[0];
-    HIP_TRY(hipSetDevice(d.hip_id));
-    cbx::LaunchConfig cfg = p->avg_cfg;
-    cfg.num_cus = d.num_cus;
-    HIP_TRY(cbx::launch_averaging_fused(model, range(args[0], 0, p->n4b, true), cfg,
-                                        static_cast<hipStream_t>(streams[0]), p->next_timing()));
+    PlanLane &l = lanes[0];
+    TRY(l.select());
+    HIP_TRY(cbx::launch_averaging_fused(model, with_tail(args[0], p->n4b, p->n, 0), l.on_device(p->avg_cfg), l.stream,
+                                        p->next_timing()));
     return copies;
   }
-  const int64_t pad = cbx::kPadFloat4;
-  int64_t nb = p->buckets > 0 ? p->buckets : kDefaultBuckets;
-  int64_t b4 = p->n4b;
-  if (nb > 1 && p->n4b > 0) b4 = ((p->n4b + nb - 1) / nb + pad - 1) / pad * pad;
-  nb = b4 > 0 ? (p->n4b + b4 - 1) / b4 : 1;
-  const bool piped = nb > 1;
-  if (piped) TRY(ensure_pipeline(p, nb));
-  auto start_of = [&](int64_t b) { return b * b4; };
-  auto len_of = [&](int64_t b) { return std::min(b4, p->n4b - b * b4); };
-  auto apply = [&](int64_t b) -> int {
-    for (int k = 0; k < G; ++k) {
-      auto &d = p->devs[k];
-      hipStream_t st = static_cast<hipStream_t>(streams[k]);
-      HIP_TRY(hipSetDevice(d.hip_id));
-      if (piped) HIP_TRY(hipStreamWaitEvent(st, d.ev_r[b], 0));
-      cbx::LaunchConfig cfg = p->apply_cfg;
-      cfg.num_cus = d.num_cus;
-      HIP_TRY(cbx::launch_averaging_apply(model, range(args[k], start_of(b), len_of(b), b == nb - 1), cfg, st));
-    }
-    return CBX_OK;
-  };
-  for (int64_t b = 0; b < nb; ++b) {
-    for (int k = 0; k < G; ++k) {
-      auto &d = p->devs[k];
-      hipStream_t st = static_cast<hipStream_t>(streams[k]);
-      HIP_TRY(hipSetDevice(d.hip_id));
-      cbx::LaunchConfig cfg = p->avg_cfg;
-      cfg.num_cus = d.num_cus;
-      HIP_TRY(cbx::launch_averaging_accumulate(model, range(args[k], start_of(b), len_of(b), b == nb - 1), cfg, st));
-      if (piped) {
-        HIP_TRY(hipEventRecord(d.ev_a[b], st));
-        HIP_TRY(hipStreamWaitEvent(d.comm_stream, d.ev_a[b], 0));
-      }
-    }
-    NCCL_TRY(ncclGroupStart());
-    for (int k = 0; k < G; ++k) {
-      auto &d = p->devs[k];
-      HIP_TRY(hipSetDevice(d.hip_id));
-      const int64_t lo_f = start_of(b) * 4;
-      const int64_t hi_f = b == nb - 1 ? p->n : (start_of(b) + len_of(b)) * 4;
-      NCCL_TRY(ncclAllReduce(d.acc_ctrl + cbx::kCtrlFloats + lo_f, d.D_ctrl + cbx::kCtrlFloats + lo_f,
-                             (size_t)(hi_f - lo_f), ncclFloat, ncclSum, d.comm,
-                             piped ? d.comm_stream : static_cast<hipStream_t>(streams[k])));
-    }
-    NCCL_TRY(ncclGroupEnd());
-    if (piped) {
-      for (int k = 0; k < G; ++k) {
-        auto &d = p->devs[k];
-        HIP_TRY(hipSetDevice(d.hip_id));
-        HIP_TRY(hipEventRecord(d.ev_r[b], d.comm_stream));
-      }
-      if (b >= 1) TRY(apply(b - 1));
-    }
-  }
-  TRY(apply(nb - 1));
+  TRY(accumulate_reduce_apply(lanes, grid, group_begin, group_end));
   return copies;
 }
 
@@ -437,7 +437,6 @@ int cbx_sma_plan_step(cbx_sma_plan *p, void *const *streams, float *const *z, fl
   if (first < 0 || first > nreplicas) return fail(CBX_ERR_INVALID, "first replica %d out of range", first);
   const bool mom = momentum > 0.0f;  // sma.c:150: base momentum forced to 0.9 when > 0
   if (mom && !last) return fail(CBX_ERR_INVALID, "base momentum > 0 needs the base models' last buffers");
-  // Per device: its locked replicas from `first` on, in id order (sma.c:69-73).
   std::vector<cbx::SmaArgs> args(G);
   int copies_total = 0;
   for (int k = 0; k < G; ++k) {
@@ -445,23 +444,23 @@ int cbx_sma_plan_step(cbx_sma_plan *p, void *const *streams, float *const *z, fl
     if (!z[k] || !aligned16(z[k]) || (mom && (!last[k] || !aligned16(last[k]))))
       return fail(CBX_ERR_INVALID, "device %d: base buffers must be non-null and 16-byte aligned", k);
   }
-  for (int id = first; id < nreplicas; ++id) {
-    if (!locked[id]) continue;
-    const int k = replica_device[id];
-    if (k < 0 || k >= G) return fail(CBX_ERR_INVALID, "replica %d on device %d of %d", id, k, G);
-    if (!w[id] || !s[id] || !aligned16(w[id]) || !aligned16(s[id]))
-      return fail(CBX_ERR_INVALID, "replica %d: buffers must be non-null and 16-byte aligned", id);
-    cbx::SmaArgs &a = args[k];
-    if (a.nrep >= cbx::kMaxReplicas)
-      return fail(CBX_ERR_UNSUPPORTED, "more than %d locked replicas on one device", cbx::kMaxReplicas);
-    a.s[a.nrep] = reinterpret_cast<const cbx::v4f *>(s[id]);
-    a.w[a.nrep] = reinterpret_cast<cbx::v4f *>(w[id]);
-    if (copy[id]) {
-      a.copies += 1.0f;  // sma.c:113-120
-      ++copies_total;
-    }
-    ++a.nrep;
-  }
+  TRY(gather_replicas(args, first, nreplicas, replica_device, locked, w, s, kBadReplicaBuffers,
+                      [&](cbx::SmaArgs &a, int id) {
+                        a.s[a.nrep] = reinterpret_cast<const cbx::v4f *>(s[id]);
+                        if (copy[id]) {
+                          a.copies += 1.0f;  // sma.c:113-120
+                          ++copies_total;
+                        }
+                      }));
+  // G > 1: kernel A, the grouped all-reduce of the control block + acc
+  // (common.c:14-54), kernel B.  One bucket: everything in order on each
+  // device's stream, the reference's structure.  nb > 1 buckets (the
+  // default): the all-reduce of bucket k runs on a stream of the plan's,
+  // beside kernel A of bucket k+1 (accumulate_reduce_apply, bucket_pipeline.h).
+  // The control block rides bucket 0; the tail rides the last bucket.
+  const BucketGrid grid = BucketGrid::by_count(p->n4b, p->buckets);
+  if (p->ranks > 1 && grid.nb > 1) TRY(ensure_pipeline(p, grid.nb));
+  std::vector<SmaPlanLane> lanes;
   for (int k = 0; k < G; ++k) {
     auto &d = p->devs[k];
     cbx::SmaArgs &a = args[k];
@@ -473,101 +472,18 @@ int cbx_sma_plan_step(cbx_sma_plan *p, void *const *streams, float *const *z, fl
     a.ctrl_in = d.D_ctrl;
     a.n4 = p->n4b;
     a.alpha = alpha;  // sma.c:33
+    lanes.push_back({PlanLane(p, k, streams, d.acc_ctrl + cbx::kCtrlFloats, true), a, mom});
   }
-  // The elements past the last whole trip, done by extra workgroups of the
-  // launch that covers the buffers' end; float indices relative to the
-  // launch's pointers (offset by start4 float4s).
-  auto with_tail = [&](cbx::SmaArgs a, int64_t start4) {
-    a.tail_lo = (p->n4b - start4) * 4;
-    a.tail_hi = p->n - start4 * 4;
-    return a;
-  };
   if (p->ranks == 1) {
     // One GPU: the all-reduce of one buffer is the identity, so Phases A + C
     // (+ D) fuse into one pass, as in the context's G = 1 step.
-    auto &d = p->devs[0];
-    hipStream_t st = static_cast<hipStream_t>(streams[0]);
-    HIP_TRY(hipSetDevice(d.hip_id));
-    cbx::LaunchConfig cfg = p->cfg;
-    cfg.num_cus = d.num_cus;
-    HIP_TRY(cbx::launch_sma_fused(with_tail(args[0], 0), mom, copies_total > 0, cfg, st, p->next_timing()));
+    PlanLane &l = lanes[0];
+    TRY(l.select());
+    HIP_TRY(cbx::launch_sma_fused(with_tail(args[0], p->n4b, p->n, 0), mom, copies_total > 0, l.on_device(p->cfg),
+                                  l.stream, p->next_timing()));
     return copies_total > 0 ? 1 : 0;
   }
-  // G > 1: kernel A, the grouped all-reduce of the control block + acc
-  // (common.c:14-54), kernel B.  One bucket: everything in order on each
-  // device's stream, the reference's structure.  nb > 1 buckets (the
-  // default): the all-reduce of bucket k runs on a stream of the plan's,
-  // beside kernel A of bucket k+1, as in the context's pipeline:
-  //   stream      : A(0) A(1) [wait r(0)] B(0) A(2) [wait r(1)] B(1) ...
-  //   comm_stream : [wait a(0)] AR(0) [wait a(1)] AR(1) ...
-  // The control block rides bucket 0; the tail rides the last bucket (its
-  // kernel A / B launches take the tail too, its all-reduce extends to n).  The next step's AR(k) waits for its A(k), which follows this
-  // step's last B on the caller's stream, so no buffer is overwritten early.
-  const int64_t pad = cbx::kPadFloat4;
-  int64_t nb = p->buckets > 0 ? p->buckets : kDefaultBuckets;
-  int64_t b4 = p->n4b;
-  if (nb > 1 && p->n4b > 0) b4 = ((p->n4b + nb - 1) / nb + pad - 1) / pad * pad;
-  nb = b4 > 0 ? (p->n4b + b4 - 1) / b4 : 1;
-  const bool piped = nb > 1;
-  if (piped) TRY(ensure_pipeline(p, nb));
-  auto start_of = [&](int64_t b) { return b * b4; };
-  auto len_of = [&](int64_t b) { return std::min(b4, p->n4b - b * b4); };
-  auto apply = [&](int64_t b) -> int {
-    for (int k = 0; k < G; ++k) {
-      auto &d = p->devs[k];
-      hipStream_t st = static_cast<hipStream_t>(streams[k]);
-      HIP_TRY(hipSetDevice(d.hip_id));
-      if (piped) HIP_TRY(hipStreamWaitEvent(st, d.ev_r[b], 0));
-      cbx::LaunchConfig cfg = p->apply_cfg;
-      cfg.num_cus = d.num_cus;
-      cbx::SmaArgs a = offset_args(args[k], start_of(b), len_of(b));
-      if (b == nb - 1) a = with_tail(a, start_of(b));
-      HIP_TRY(cbx::launch_sma_apply(a, mom, cfg, st));
-    }
-    return CBX_OK;
-  };
-  for (int64_t b = 0; b < nb; ++b) {
-    for (int k = 0; k < G; ++k) {
-      auto &d = p->devs[k];
-      hipStream_t st = static_cast<hipStream_t>(streams[k]);
-      HIP_TRY(hipSetDevice(d.hip_id));
-      cbx::LaunchConfig cfg = p->cfg;
-      cfg.num_cus = d.num_cus;
-      cbx::SmaArgs a = offset_args(args[k], start_of(b), len_of(b));
-      if (b == nb - 1) a = with_tail(a, start_of(b));
-      HIP_TRY(cbx::launch_sma_accumulate(a, b == 0, cfg, st));
-      if (piped) {
-        HIP_TRY(hipEventRecord(d.ev_a[b], st));
-        HIP_TRY(hipStreamWaitEvent(d.comm_stream, d.ev_a[b], 0));
-      }
-    }
-    NCCL_TRY(ncclGroupStart());
-    for (int k = 0; k < G; ++k) {
-      auto &d = p->devs[k];
-      HIP_TRY(hipSetDevice(d.hip_id));
-      const int64_t lo_f = start_of(b) * 4;
-      const int64_t hi_f = b == nb - 1 ? p->n : (start_of(b) + len_of(b)) * 4;
-      float *src = d.acc_ctrl + cbx::kCtrlFloats + lo_f, *dst = d.D_ctrl + cbx::kCtrlFloats + lo_f;
-      size_t count = (size_t)(hi_f - lo_f);
-      if (b == 0) {
-        src -= cbx::kCtrlFloats;
-        dst -= cbx::kCtrlFloats;
-        count += cbx::kCtrlFloats;
-      }
-      NCCL_TRY(ncclAllReduce(src, dst, count, ncclFloat, ncclSum, d.comm,
-                             piped ? d.comm_stream : static_cast<hipStream_t>(streams[k])));
-    }
-    NCCL_TRY(ncclGroupEnd());
-    if (piped) {
-      for (int k = 0; k < G; ++k) {
-        auto &d = p->devs[k];
-        HIP_TRY(hipSetDevice(d.hip_id));
-        HIP_TRY(hipEventRecord(d.ev_r[b], d.comm_stream));
-      }
-      if (b >= 1) TRY(apply(b - 1));
-    }
-  }
-  TRY(apply(nb - 1));
+  TRY(accumulate_reduce_apply(lanes, grid, group_begin, group_end));
   return copies_total > 0 ? 1 : 0;
 }
 
@@ -688,73 +604,17 @@ int cbx_ssgd_plan_step(cbx_sma_plan *p, void *const *streams, float *const *z, f
     a.ratio = (float)(1.0 / (double)(float)wpc);  // :55
     a.momentum = mom ? momentum : 0.0f;
   }
-  for (int id = first; id < nreplicas; ++id) {  // common.c:208: locked replicas from `first` on
-    if (!locked[id]) continue;
-    const int k = replica_device[id];
-    if (k < 0 || k >= G) return fail(CBX_ERR_INVALID, "replica %d on device %d of %d", id, k, G);
-    if (!w[id] || !aligned16(w[id])) return fail(CBX_ERR_INVALID, "replica %d: buffer must be 16-byte aligned", id);
-    if (args[k].nrep >= cbx::kMaxReplicas)
-      return fail(CBX_ERR_UNSUPPORTED, "more than %d locked replicas on one device", cbx::kMaxReplicas);
-    args[k].w[args[k].nrep++] = reinterpret_cast<cbx::v4f *>(w[id]);
-  }
+  TRY(gather_replicas(args, first, nreplicas, replica_device, locked, w, nullptr,
+                      "replica %d: buffer must be 16-byte aligned", [](cbx::SsgdArgs &, int) {}));
   // Buckets as in the SMA step; at G > 1 with more than one, the all-reduce
-  // of bucket k+1 runs on the plan's stream beside the apply of bucket k:
-  //   stream      : [entry] [wait r(0)] K(0) [wait r(1)] K(1) ...
-  //   comm_stream : [wait entry] AR(0) AR(1) ...
-  const int64_t pad = cbx::kPadFloat4;
-  int64_t nb = p->ranks == 1 ? 1 : (p->buckets > 0 ? p->buckets : kDefaultBuckets);
-  int64_t b4 = p->n4b;
-  if (nb > 1 && p->n4b > 0) b4 = ((p->n4b + nb - 1) / nb + pad - 1) / pad * pad;
-  nb = b4 > 0 ? (p->n4b + b4 - 1) / b4 : 1;
-  const bool piped = p->ranks > 1 && nb > 1;
-  if (piped) {
-    TRY(ensure_pipeline(p, nb));
-    for (int k = 0; k < G; ++k) {  // everything the task steps accumulated, in stream order
-      auto &d = p->devs[k];
-      HIP_TRY(hipSetDevice(d.hip_id));
-      HIP_TRY(hipEventRecord(d.ev_a[0], static_cast<hipStream_t>(streams[k])));
-      HIP_TRY(hipStreamWaitEvent(d.comm_stream, d.ev_a[0], 0));
-    }
-  }
-  for (int64_t b = 0; b < nb; ++b) {
-    const int64_t s4 = b * b4, l4 = std::min(b4, p->n4b - s4);
-    if (p->ranks > 1) {
-      NCCL_TRY(ncclGroupStart());
-      for (int k = 0; k < G; ++k) {
-        auto &d = p->devs[k];
-        HIP_TRY(hipSetDevice(d.hip_id));
-        const int64_t hi_f = b == nb - 1 ? p->n : (s4 + l4) * 4;
-        NCCL_TRY(ncclAllReduce(acc[k] + s4 * 4, d.D_ctrl + cbx::kCtrlFloats + s4 * 4, (size_t)(hi_f - s4 * 4),
-                               ncclFloat, ncclSum, d.comm,
-                               piped ? d.comm_stream : static_cast<hipStream_t>(streams[k])));
-      }
-      NCCL_TRY(ncclGroupEnd());
-    }
-    for (int k = 0; k < G; ++k) {
-      auto &d = p->devs[k];
-      hipStream_t st = static_cast<hipStream_t>(streams[k]);
-      HIP_TRY(hipSetDevice(d.hip_id));
-      if (piped) {
-        HIP_TRY(hipEventRecord(d.ev_r[b], d.comm_stream));
-        HIP_TRY(hipStreamWaitEvent(st, d.ev_r[b], 0));
-      }
-      cbx::SsgdArgs a = args[k];
-      for (int r = 0; r < a.nrep; ++r) a.w[r] += s4;
-      a.z += s4;
-      if (a.last) a.last += s4;
-      a.acc += s4;
-      a.D += s4;
-      a.n4 = l4;
-      if (b == nb - 1) {  // the elements past the last whole trip ride this launch
-        a.tail_lo = (p->n4b - s4) * 4;
-        a.tail_hi = p->n - s4 * 4;
-      }
-      cbx::LaunchConfig cfg = p->ssgd_apply_cfg;
-      cfg.num_cus = d.num_cus;
-      HIP_TRY(cbx::launch_ssgd_apply(a, cfg, st));
-    }
-  }
-  return CBX_OK;
+  // of bucket k+1 runs on the plan's stream beside the apply of bucket k
+  // (reduce_apply, bucket_pipeline.h).  One rank: no collective, one launch.
+  const BucketGrid grid = p->ranks == 1 ? BucketGrid::whole(p->n4b) : BucketGrid::by_count(p->n4b, p->buckets);
+  if (p->ranks > 1 && grid.nb > 1) TRY(ensure_pipeline(p, grid.nb));
+  std::vector<SsgdPlanLane> lanes;
+  for (int k = 0; k < G; ++k)
+    lanes.push_back({PlanLane(p, k, streams, acc[k], false), args[k]});
+  return reduce_apply(lanes, grid, p->ranks > 1, group_begin, group_end);
 }
 
 // crossbowKernelOptimiserSynchronousSGD (kernels/optimisers/synchronoussgd.cu:

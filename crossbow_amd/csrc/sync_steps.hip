@@ -2,8 +2,10 @@
 // cbx_synchronise_staged: the SMA step (clib-multigpu/synch/sma.c:13-231,
 // synch/common.c:3-57) fused at G = 1 and as kernel A / collective / kernel B
 // per bucket at G > 1, its peer-read and reduce-scatter forms, the pipelined
-// host-staged step, synchronous SGD (synch/synchronoussgd.c:13-106), and the
-// stream-order check that verifies the bucket pipeline's ordering.
+// host-staged step, synchronous SGD (synch/synchronoussgd.c:13-106), elastic
+// and Polyak-Ruppert averaging, and the stream-order check that verifies the
+// split SMA step's ordering.  The S-SGD and averaging steps are lanes of the
+// bucket pipeline whose order and geometry bucket_pipeline.h holds.
 #include "context_internal.h"
 
 namespace cbx::host {
@@ -37,20 +39,6 @@ int build_args(cbx_context *c, Device &d, int first, cbx::SmaArgs &a, int *copie
   a.copies = (float)cp;
   *copies = cp;
   return CBX_OK;
-}
-
-cbx::SmaArgs offset_args(const cbx::SmaArgs &a, int64_t start4, int64_t len4) {
-  cbx::SmaArgs b = a;
-  for (int r = 0; r < a.nrep; ++r) {
-    b.s[r] = a.s[r] + start4;
-    b.w[r] = a.w[r] + start4;
-  }
-  b.z = a.z + start4;
-  if (a.last) b.last = a.last + start4;
-  b.acc = a.acc + start4;
-  b.D = a.D + start4;
-  b.n4 = len4;
-  return b;
 }
 
 // The reference records synched / base->updated (sma.c:177,204) and one
@@ -615,6 +603,22 @@ inline int64_t peer_shard4(int64_t len4, int G) {
   return ((len4 + G - 1) / G + pad - 1) / pad * pad;
 }
 
+// The events of `nb` buckets on the current device.  The three vectors grow
+// together (SplitStep indexes all of them); acc / b are also handed to kernel
+// dispatches as their stop events, so they are timed.
+int ensure_bucket_events(Device &d, int64_t nb) {
+  while ((int64_t)d.bucket_red.size() < nb) {
+    hipEvent_t ea, er, eb;
+    HIP_TRY(hipEventCreate(&ea));
+    HIP_TRY(hipEventCreateWithFlags(&er, hipEventDisableTiming));
+    HIP_TRY(hipEventCreate(&eb));
+    d.bucket_acc.push_back(ea);
+    d.bucket_red.push_back(er);
+    d.bucket_b.push_back(eb);
+  }
+  return CBX_OK;
+}
+
 // ---------------------------------------------------------------------------
 // The split SMA step (G > 1, or forced at G = 1): kernel A, the collective of
 // acc (+ control block), kernel B.  With one bucket everything runs in order
@@ -802,15 +806,9 @@ struct SplitStep {
 
   // Bucket geometry and the step's modes, for every device.
   int prepare_common() {
-    const int64_t pad = cbx::kPadFloat4;
-    b4 = c->n4;
-    if (c->bucket_elems > 0) {
-      b4 = ((c->bucket_elems / 4 + pad - 1) / pad) * pad;
-    } else if (c->G > 1) {
-      b4 = ((c->n4 / kDefaultBuckets + pad - 1) / pad) * pad;  // auto: kDefaultBuckets buckets
-    }
-    if (b4 <= 0 || b4 > c->n4) b4 = c->n4;
-    nb = (c->n4 + b4 - 1) / b4;
+    const BucketGrid grid = BucketGrid::by_elements(c->n4, c->bucket_elems, c->G);
+    b4 = grid.b4;
+    nb = grid.nb;
     pipelined = nb > 1;
     cross = pipelined && c->pipeline_mode == 1;
     rsag = c->allreduce_algo == CBX_ALLREDUCE_RSAG;
@@ -857,18 +855,7 @@ struct SplitStep {
     {
       Device &d = c->devs[k];
       HIP_TRY(hipSetDevice(d.hip_id));
-      if (pipelined) {
-        while ((int64_t)d.bucket_acc.size() < nb) {
-          hipEvent_t ea, er, eb;
-          // ea / eb are also handed to kernel dispatches as their stop events.
-          HIP_TRY(hipEventCreate(&ea));
-          HIP_TRY(hipEventCreateWithFlags(&er, hipEventDisableTiming));
-          HIP_TRY(hipEventCreate(&eb));
-          d.bucket_acc.push_back(ea);
-          d.bucket_red.push_back(er);
-          d.bucket_b.push_back(eb);
-        }
-      }
+      if (pipelined) TRY(ensure_bucket_events(d, nb));
       if (cross) {
         if (!d.cross_entry) {
           HIP_TRY(hipEventCreateWithFlags(&d.cross_entry, hipEventDisableTiming));
@@ -956,7 +943,7 @@ struct SplitStep {
         HIP_TRY(cbx::launch_order_probe(st, {nullptr, o.pa[b]}));
         o.a1[b] = t.stop;  // with timing on, A always carries a stop event (the pool's or the ring's)
       }
-      HIP_TRY(cbx::launch_sma_accumulate(offset_args(args[k], start_of(b), len_of(b)), b == 0, cfg, st, t));
+      HIP_TRY(cbx::launch_sma_accumulate(range_of(args[k], start_of(b), len_of(b)), b == 0, cfg, st, t));
       if (peer && !pipelined && !ipc) HIP_TRY(hipEventRecord(d.peer_a, st));  // the other devices' R waits on it
       TRY(put_flag(st, kIpcA, b));  // one process per GPU: the other ranks' R waits on it
       if (ipc && b == std::min<int64_t>(c->fault_peer_fail_bucket, nb - 1) && c->fault_peer_fail_rank == c->ipc.me &&
@@ -1065,7 +1052,7 @@ struct SplitStep {
       for (size_t k = k0; mom && k < k1; ++k) {
         Device &d = c->devs[k];
         HIP_TRY(hipSetDevice(d.hip_id));
-        cbx::SmaArgs a = offset_args(args[k], start + d.g * sh4, sh4);
+        cbx::SmaArgs a = range_of(args[k], start + d.g * sh4, sh4);
         cbx::LaunchConfig cfg = c->apply_cfg;
         cfg.num_cus = d.num_cus;
         HIP_TRY(cbx::launch_sma_shard_momentum(a, cfg, on_comm ? d.comm_stream : d.stream));
@@ -1149,7 +1136,7 @@ struct SplitStep {
       cfg.num_cus = d.num_cus;
       cbx::Timing t;
       if (b == nb - 1) t.stop = step_stop_event(c, d, EV_B);
-      cbx::SmaArgs a = offset_args(args[k], start_of(b), len_of(b));
+      cbx::SmaArgs a = range_of(args[k], start_of(b), len_of(b));
       if (rsag && mom) a.D = a.last;  // the gathered D' (kernel B then adds it without momentum)
       if (cross) {
         // The next step's AR(0) may overwrite D's control block before this
@@ -1594,7 +1581,7 @@ int sma_step_staged(cbx_context *c, int first, int buckets) {
       HIP_TRY(hipSetDevice(d.hip_id));
       cbx::LaunchConfig cfg = c->cfg;
       cfg.num_cus = d.num_cus;
-      const cbx::SmaArgs a = offset_args(args[k], s4, l4);
+      const cbx::SmaArgs a = range_of(args[k], s4, l4);
       if (fused) HIP_TRY(cbx::launch_sma_fused(a, mom, copies_total > 0, cfg, d.stream));
       else HIP_TRY(cbx::launch_sma_accumulate(a, b == 0, cfg, d.stream));
     }
@@ -1618,7 +1605,7 @@ int sma_step_staged(cbx_context *c, int first, int buckets) {
         HIP_TRY(hipSetDevice(d.hip_id));
         cbx::LaunchConfig cfg = c->apply_cfg;
         cfg.num_cus = d.num_cus;
-        HIP_TRY(cbx::launch_sma_apply(offset_args(args[k], s4, l4), mom, cfg, d.stream));
+        HIP_TRY(cbx::launch_sma_apply(range_of(args[k], s4, l4), mom, cfg, d.stream));
       }
     }
     // outputs: z, last, w_i (cbx_stage_out's set)
@@ -1663,11 +1650,36 @@ int sma_step_staged(cbx_context *c, int first, int buckets) {
 }
 
 // ---------------------------------------------------------------------------
+// A lane of a bucketed step over the context's arena (bucket_pipeline.h holds
+// the order): the sync stream and comm_stream, the bucket events, and the
+// all-reduce of base->gradient into base->diff.
+// ---------------------------------------------------------------------------
+PipelineLane context_lane(cbx_context *c, Device &d) {
+  return {d.hip_id, d.num_cus, d.stream, d.comm_stream, d.bucket_acc, d.bucket_red, d.comm,
+          base_dev(c, d, CBX_BUF_GRADIENT), base_dev(c, d, CBX_BUF_DIFF), c->n4 * 4, false};
+}
+
+// ---------------------------------------------------------------------------
 // Synchronous SGD barrier (update model WORKER), synch/synchronoussgd.c:13-106
 // with common.c:3-57 (all-reduce) and :198-220 (base -> replicas).  The
 // reference's SINGLE_GPU variant is disabled like SMA's (:5-11); G = 1 runs
 // the multi-GPU algorithm with an identity all-reduce, in one kernel.
 // ---------------------------------------------------------------------------
+struct SsgdLane : PipelineLane {
+  cbx_context *c;
+  Device &d;
+  const cbx::SsgdArgs &args;
+  bool split;
+  int launch_k(const Bucket &b) {
+    cbx::Timing t;
+    if (!split) t.start = ring_event(c, d, EV_START);
+    if (b.last) t.stop = step_stop_event(c, d, split ? EV_B : EV_A);
+    HIP_TRY(cbx::launch_ssgd_apply(range_of(args, b.start4, b.len4), on_device(c->ssgd_apply_cfg), stream, t));
+    if (b.last) ring_advance(c, d, split ? 2 : 0);
+    return CBX_OK;
+  }
+};
+
 int ssgd_step(cbx_context *c, int first) {
   if (c->model.wpc <= 0) return fail(CBX_ERR_STATE, "S-SGD needs the work per clock (setModelWorkPerClock)");
   const float ratio = (float)(1.0 / (double)(float)c->model.wpc);  // synchronoussgd.c:55
@@ -1695,72 +1707,18 @@ int ssgd_step(cbx_context *c, int first) {
     a.momentum = mom ? c->model.conf.momentum : 0.0f;
   }
   // Buckets as in the SMA split pipeline (cbx_set_bucket_elements; 8 by
-  // default at G > 1).  With more than one, the all-reduce of bucket k+1
-  // runs on comm_stream beside the apply kernel of bucket k:
-  //   stream      : [entry] [wait red(0)] K(0) [wait red(1)] K(1) ...
-  //   comm_stream : [wait entry] AR(0) AR(1) ...
-  int64_t b4 = c->n4, nb = 1;
-  if (split) {
-    const int64_t pad = cbx::kPadFloat4;
-    if (c->bucket_elems > 0) b4 = ((c->bucket_elems / 4 + pad - 1) / pad) * pad;
-    else if (c->G > 1) b4 = ((c->n4 / kDefaultBuckets + pad - 1) / pad) * pad;
-    if (b4 <= 0 || b4 > c->n4) b4 = c->n4;
-    nb = (c->n4 + b4 - 1) / b4;
+  // default at G > 1); the order is reduce_apply's (bucket_pipeline.h).
+  const BucketGrid grid = split ? BucketGrid::by_elements(c->n4, c->bucket_elems, c->G) : BucketGrid::whole(c->n4);
+  std::vector<SsgdLane> lanes;
+  for (size_t k = 0; k < c->devs.size(); ++k) {
+    Device &d = c->devs[k];
+    lanes.push_back({context_lane(c, d), c, d, args[k], split});
+    if (!split) continue;
+    HIP_TRY(hipSetDevice(d.hip_id));
+    TRY(mark(c, d, EV_START));
+    if (grid.nb > 1) TRY(ensure_bucket_events(d, grid.nb));
   }
-  const bool pipelined = nb > 1;
-  if (split) {
-    for (Device &d : c->devs) {
-      HIP_TRY(hipSetDevice(d.hip_id));
-      TRY(mark(c, d, EV_START));
-      if (!pipelined) continue;
-      while ((int64_t)d.bucket_red.size() < nb) {
-        hipEvent_t ea, er, eb;
-        HIP_TRY(hipEventCreate(&ea));
-        HIP_TRY(hipEventCreateWithFlags(&er, hipEventDisableTiming));
-        HIP_TRY(hipEventCreate(&eb));
-        d.bucket_acc.push_back(ea);
-        d.bucket_red.push_back(er);
-        d.bucket_b.push_back(eb);
-      }
-      // everything the task steps accumulated into acc, in sync-stream order
-      HIP_TRY(hipEventRecord(d.bucket_acc[0], d.stream));
-      HIP_TRY(hipStreamWaitEvent(d.comm_stream, d.bucket_acc[0], 0));
-    }
-  }
-  for (int64_t b = 0; b < nb; ++b) {
-    const int64_t start = b * b4, len = std::min(b4, c->n4 - start);
-    if (split) {
-      NCCL_TRY(ncclGroupStart());
-      for (Device &d : c->devs) {
-        HIP_TRY(hipSetDevice(d.hip_id));
-        NCCL_TRY(ncclAllReduce(base_dev(c, d, CBX_BUF_GRADIENT) + start * 4, base_dev(c, d, CBX_BUF_DIFF) + start * 4,
-                               (size_t)len * 4, ncclFloat, ncclSum, d.comm, pipelined ? d.comm_stream : d.stream));
-      }
-      NCCL_TRY(ncclGroupEnd());
-    }
-    for (size_t k = 0; k < c->devs.size(); ++k) {
-      Device &d = c->devs[k];
-      HIP_TRY(hipSetDevice(d.hip_id));
-      if (pipelined) {
-        HIP_TRY(hipEventRecord(d.bucket_red[b], d.comm_stream));
-        HIP_TRY(hipStreamWaitEvent(d.stream, d.bucket_red[b], 0));
-      }
-      cbx::LaunchConfig cfg = c->ssgd_apply_cfg;
-      cfg.num_cus = d.num_cus;
-      cbx::Timing t;
-      if (!split) t.start = ring_event(c, d, EV_START);
-      if (b == nb - 1) t.stop = step_stop_event(c, d, split ? EV_B : EV_A);
-      cbx::SsgdArgs a = args[k];
-      for (int r = 0; r < a.nrep; ++r) a.w[r] += start;
-      a.z += start;
-      if (a.last) a.last += start;
-      a.acc += start;
-      a.D += start;
-      a.n4 = len;
-      HIP_TRY(cbx::launch_ssgd_apply(a, cfg, d.stream, t));
-      if (b == nb - 1) ring_advance(c, d, split ? 2 : 0);
-    }
-  }
+  TRY(reduce_apply(lanes, grid, split, group_begin, group_end));
   c->last_step_split = split;
   return finish_step(c);
 }
@@ -1773,13 +1731,31 @@ int ssgd_step(cbx_context *c, int first) {
 // every device applies D to its z (kernel B): the reference chains every
 // replica into the default device's acc over peer copies and broadcasts z,
 // so the two differ in summation order only, and z is the same bits on every
-// device.  Buckets as in ssgd_step; with more than one, the
-// all-reduce of bucket k runs on comm_stream beside kernel A of bucket k + 1:
-//   stream      : A(0) A(1) [wait red(0)] B(0) A(2) [wait red(1)] B(1) ...
-//   comm_stream : [wait acc(0)] AR(0) [wait acc(1)] AR(1) ...
-// The next step's A(0) follows this step's last B on the same stream, and
-// its AR(k) waits for its A(k): no buffer is rewritten while still in use.
+// device.  Buckets as in ssgd_step; the order is
+// accumulate_reduce_apply's (bucket_pipeline.h).
 // ---------------------------------------------------------------------------
+struct AveragingLane : PipelineLane {
+  cbx_context *c;
+  Device &d;
+  cbx::AvgModel model;
+  const cbx::AvgArgs &args;
+  bool pipelined;
+  int launch_a(const Bucket &b) {
+    cbx::Timing t;
+    if (!pipelined) t = {ring_event(c, d, EV_START), ring_event(c, d, EV_A)};
+    HIP_TRY(cbx::launch_averaging_accumulate(model, range_of(args, b.start4, b.len4), on_device(c->avg_cfg), stream, t));
+    return CBX_OK;
+  }
+  int launch_b(const Bucket &b) {
+    if (!pipelined) TRY(mark(c, d, EV_AR));  // in order: the all-reduce is on this stream
+    cbx::Timing t;
+    if (b.last) t.stop = step_stop_event(c, d, EV_B);
+    HIP_TRY(cbx::launch_averaging_apply(model, range_of(args, b.start4, b.len4), on_device(c->apply_cfg), stream, t));
+    if (b.last) ring_advance(c, d, pipelined ? 2 : 1);
+    return CBX_OK;
+  }
+};
+
 int averaging_step(cbx_context *c, int first, int clock, bool polyak) {
   // polyakruppert.c:16 divides by clock + 1: the caller has refused clock < 0
   const bool split = c->G > 1 || c->force_split;
@@ -1812,19 +1788,6 @@ int averaging_step(cbx_context *c, int first, int clock, bool polyak) {
     a.scale = (float)(1.0 / (double)(float)c->size.load());  // polyakruppert.c:15
     a.running = (float)(1.0 / (double)(float)(clock + 1));   // :16
   }
-  auto range = [](const cbx::AvgArgs &a, int64_t start4, int64_t len4) {
-    cbx::AvgArgs b = a;
-    for (int r = 0; r < a.nrep; ++r) {
-      b.s[r] = a.s[r] + start4;
-      b.w[r] = a.w[r] + start4;
-    }
-    b.z = a.z + start4;
-    if (a.last) b.last = a.last + start4;
-    b.acc = a.acc + start4;
-    b.D = a.D + start4;
-    b.n4 = len4;
-    return b;
-  };
   if (!split) {
     Device &d = c->devs[0];
     HIP_TRY(hipSetDevice(d.hip_id));
@@ -1834,72 +1797,18 @@ int averaging_step(cbx_context *c, int first, int clock, bool polyak) {
                                         {step_start_event(c, d, 0), step_stop_event(c, d, EV_A)}));
     ring_advance(c, d, 0);
   } else {
-    int64_t b4 = c->n4;
-    const int64_t pad = cbx::kPadFloat4;
-    if (c->bucket_elems > 0) b4 = ((c->bucket_elems / 4 + pad - 1) / pad) * pad;
-    else if (c->G > 1) b4 = ((c->n4 / kDefaultBuckets + pad - 1) / pad) * pad;
-    if (b4 <= 0 || b4 > c->n4) b4 = c->n4;
-    const int64_t nb = (c->n4 + b4 - 1) / b4;
-    const bool pipelined = nb > 1;
-    for (Device &d : c->devs) {
+    const BucketGrid grid = BucketGrid::by_elements(c->n4, c->bucket_elems, c->G);
+    const bool pipelined = grid.nb > 1;
+    std::vector<AveragingLane> lanes;
+    for (size_t k = 0; k < c->devs.size(); ++k) {
+      Device &d = c->devs[k];
+      lanes.push_back({context_lane(c, d), c, d, model, args[k], pipelined});
+      if (!pipelined) continue;
       HIP_TRY(hipSetDevice(d.hip_id));
-      if (pipelined) TRY(mark(c, d, EV_START));
-      while (pipelined && (int64_t)d.bucket_red.size() < nb) {
-        hipEvent_t ea, er, eb;
-        HIP_TRY(hipEventCreate(&ea));
-        HIP_TRY(hipEventCreateWithFlags(&er, hipEventDisableTiming));
-        HIP_TRY(hipEventCreate(&eb));
-        d.bucket_acc.push_back(ea);
-        d.bucket_red.push_back(er);
-        d.bucket_b.push_back(eb);
-      }
+      TRY(mark(c, d, EV_START));
+      TRY(ensure_bucket_events(d, grid.nb));
     }
-    // Kernel B of bucket b on every device, once its all-reduce has landed.
-    auto apply = [&](int64_t b) -> int {
-      const int64_t start = b * b4, len = std::min(b4, c->n4 - start);
-      for (size_t k = 0; k < c->devs.size(); ++k) {
-        Device &d = c->devs[k];
-        HIP_TRY(hipSetDevice(d.hip_id));
-        if (pipelined) HIP_TRY(hipStreamWaitEvent(d.stream, d.bucket_red[b], 0));
-        cbx::LaunchConfig cfg = c->apply_cfg;
-        cfg.num_cus = d.num_cus;
-        cbx::Timing t;
-        if (b == nb - 1) t.stop = step_stop_event(c, d, EV_B);
-        HIP_TRY(cbx::launch_averaging_apply(model, range(args[k], start, len), cfg, d.stream, t));
-        if (b == nb - 1) ring_advance(c, d, pipelined ? 2 : 1);
-      }
-      return CBX_OK;
-    };
-    for (int64_t b = 0; b < nb; ++b) {
-      const int64_t start = b * b4, len = std::min(b4, c->n4 - start);
-      for (size_t k = 0; k < c->devs.size(); ++k) {
-        Device &d = c->devs[k];
-        HIP_TRY(hipSetDevice(d.hip_id));
-        cbx::LaunchConfig cfg = c->avg_cfg;
-        cfg.num_cus = d.num_cus;
-        cbx::Timing t;
-        if (!pipelined) t = {ring_event(c, d, EV_START), ring_event(c, d, EV_A)};
-        HIP_TRY(cbx::launch_averaging_accumulate(model, range(args[k], start, len), cfg, d.stream, t));
-        if (pipelined) {
-          HIP_TRY(hipEventRecord(d.bucket_acc[b], d.stream));
-          HIP_TRY(hipStreamWaitEvent(d.comm_stream, d.bucket_acc[b], 0));
-        }
-      }
-      NCCL_TRY(ncclGroupStart());
-      for (Device &d : c->devs) {
-        HIP_TRY(hipSetDevice(d.hip_id));
-        NCCL_TRY(ncclAllReduce(base_dev(c, d, CBX_BUF_GRADIENT) + start * 4, base_dev(c, d, CBX_BUF_DIFF) + start * 4,
-                               (size_t)len * 4, ncclFloat, ncclSum, d.comm, pipelined ? d.comm_stream : d.stream));
-      }
-      NCCL_TRY(ncclGroupEnd());
-      for (Device &d : c->devs) {
-        HIP_TRY(hipSetDevice(d.hip_id));
-        if (pipelined) HIP_TRY(hipEventRecord(d.bucket_red[b], d.comm_stream));
-        else TRY(mark(c, d, EV_AR));
-      }
-      if (b > 0) TRY(apply(b - 1));
-    }
-    TRY(apply(nb - 1));
+    TRY(accumulate_reduce_apply(lanes, grid, group_begin, group_end));
   }
   for (Device &d : c->devs) d.cross_valid = false;
   c->last_step_split = split;

@@ -24,7 +24,8 @@ def test_watchdog_fires_on_a_stalled_phase():
 
 def test_lib_buckets_matches_the_library_rule():
     # bench.py's config.buckets: the library's bucket geometry (whole
-    # 1,024-float4 units, SplitStep::prepare_common)
+    # 1,024-float4 units, BucketGrid::by_elements of
+    # crossbow_amd/csrc/bucket_pipeline.h)
     sys.path.insert(0, ROOT)
     import bench
     n = 25_557_032
