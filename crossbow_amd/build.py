@@ -4,7 +4,11 @@
   csrc/context.hip + csrc/sync_steps.hip + csrc/sma_kernels.hip +
   csrc/averaging_kernels.hip + csrc/sma_seam.hip + csrc/stats_kernels.hip +
   csrc/variable_rate_kernels.hip + csrc/clip_kernels.hip +
-  csrc/task_barrier_kernels.hip, linked against RCCL.
+  csrc/task_barrier_kernels.hip, linked against RCCL and against
+* ``crossbow_amd/libcrossbow_sma_variables.so`` -- the fused task-step barrier
+  with a learning rate per variable (csrc/task_barrier_variables_kernels.hip):
+  a shared object of its own, built first, so the device code of
+  ``libcrossbow_sma.so`` (``code_object_digest``) stays what it was.
 * ``crossbow_amd/libGPU.so``           -- the JNI shim exporting Crossbow's
   ``TheGPU`` model-path natives; built only where ``jni.h`` exists (there is
   no JDK in this image).
@@ -23,6 +27,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libcrossbow_sma.so")
+VARIABLES_LIB = os.path.join(PKG, "libcrossbow_sma_variables.so")
 JNI_LIB = os.path.join(PKG, "libGPU.so")
 ARCH = "gfx950"
 
@@ -36,16 +41,17 @@ def _hipcc() -> str:
 
 SOURCES = ("context.hip", "sync_steps.hip", "sma_kernels.hip", "averaging_kernels.hip", "sma_seam.hip",
            "stats_kernels.hip", "variable_rate_kernels.hip", "clip_kernels.hip", "task_barrier_kernels.hip")
+VARIABLES_SOURCES = ("task_barrier_variables_kernels.hip",)
 HEADERS = ("context_internal.h", "sma_internal.h", "stream_helpers.h", "stats_internal.h", "stats_plan.h",
            "optimise_plan.h", "clip_internal.h", "bucket_pipeline.h")
 
 
-def _sources():
-    return [os.path.join(CSRC, f) for f in SOURCES]
+def _sources(names=SOURCES):
+    return [os.path.join(CSRC, f) for f in names]
 
 
 def _deps():
-    return _sources() + [os.path.join(CSRC, f) for f in HEADERS] + [os.path.join(ROOT, "include", "crossbow_sma.h"),
+    return _sources() + _sources(VARIABLES_SOURCES) + [os.path.join(CSRC, f) for f in HEADERS] + [os.path.join(ROOT, "include", "crossbow_sma.h"),
                                                                    os.path.abspath(__file__)]
 
 
@@ -56,14 +62,9 @@ def _stale(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build_lib(force: bool = False, verbose: bool = False) -> str:
-    if not force and not _stale(LIB, _deps()):
-        return LIB
-    tmp = LIB + ".tmp"
-    objdir = os.path.join(PKG, "build")
-    os.makedirs(objdir, exist_ok=True)
+def _compile(sources, objdir, verbose):
     objs = []
-    for src in _sources():
+    for src in sources:
         stem = os.path.splitext(os.path.basename(src))[0]
         obj = os.path.join(objdir, stem + ".o")
         cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall",
@@ -79,12 +80,29 @@ def build_lib(force: bool = False, verbose: bool = False) -> str:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
         objs.append(obj)
-    cmd = [_hipcc(), f"--offload-arch={ARCH}", "-shared", "-o", tmp] + objs + \
-        ["-lrccl", "-lrocprofiler-sdk-roctx", "-lpthread"]
+    return objs
+
+
+def _link(target, objs, libs, verbose):
+    tmp = target + ".tmp"
+    cmd = [_hipcc(), f"--offload-arch={ARCH}", "-shared", "-o", tmp] + objs + libs
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.run(cmd, check=True)
-    os.replace(tmp, LIB)
+    os.replace(tmp, target)
+
+
+def build_lib(force: bool = False, verbose: bool = False) -> str:
+    # one staleness check for both libraries: they share the headers
+    if not force and not _stale(LIB, _deps()) and not _stale(VARIABLES_LIB, _deps()):
+        return LIB
+    objdir = os.path.join(PKG, "build")
+    os.makedirs(objdir, exist_ok=True)
+    # the object of the per-variable fused barrier first: the library links against it
+    _link(VARIABLES_LIB, _compile(_sources(VARIABLES_SOURCES), objdir, verbose), [], verbose)
+    _link(LIB, _compile(_sources(), objdir, verbose),
+          ["-L", PKG, "-lcrossbow_sma_variables", "-Wl,-rpath,$ORIGIN", "-lrccl", "-lrocprofiler-sdk-roctx", "-lpthread"],
+          verbose)
     return LIB
 
 

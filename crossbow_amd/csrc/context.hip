@@ -296,6 +296,8 @@ int cbx_set_model_variable_learning_rate_multiplier(cbx_context *c, int id, int 
         HIP_TRY(hipSetDevice(d.hip_id));
         HIP_TRY(hipDeviceSynchronize());
         HIP_TRY(hipMemcpy(d.var_tables.mult + v, &multiplier, sizeof(float), hipMemcpyHostToDevice));
+        if (d.var_tables_padded.mult)
+          HIP_TRY(hipMemcpy(d.var_tables_padded.mult + v, &multiplier, sizeof(float), hipMemcpyHostToDevice));
       }
     }
   }
@@ -451,10 +453,21 @@ static int build_variable_tables(cbx_context *c) {
     if ((int)ov.size() < sv.order) ov.resize((size_t)sv.order, -1);
     ov[(size_t)sv.order - 1] = (int)v;
   }
+  // The fused barrier sweeps the padded buffers (c->n4 float4s): its tables run
+  // over the padded length, the pad a last pseudo-variable of multiplier 1.
+  // (A model so large that only its padded length passes the builder's limit
+  // keeps the plain tables; the fused call then refuses.)
+  cbx::OptimisePlan padded;
+  const bool have_padded = cbx::build_padded_optimise_plan(elems.data(), (int)V, c->n, c->n4 * 4, &padded);
+  std::vector<float> padded_mult(c->var_mult);
+  padded_mult.push_back(1.0f);
   for (Device &d : c->devs) {
     HIP_TRY(hipSetDevice(d.hip_id));
     HIP_TRY(cbx::var_tables_upload(d.var_tables, plan.chunks.data(), plan.chunks.size(), plan.bounds.data(),
                                    c->var_mult.data(), (uint32_t)V));
+    if (have_padded)
+      HIP_TRY(cbx::var_tables_upload(d.var_tables_padded, padded.chunks.data(), padded.chunks.size(),
+                                     padded.bounds.data(), padded_mult.data(), (uint32_t)V + 1));
   }
   c->var_bounds = plan.bounds;
   return CBX_OK;
@@ -679,10 +692,13 @@ int cbx_synchronise_staged(cbx_context *c, int first, int clock, int autotune, i
 // The pending task steps of the locked replicas and the one-GPU SMA barrier in
 // one launch (task_barrier_kernels.hip).  Everything is validated before the
 // first side effect: a refused call leaves buffers, flags and clocks alone.
-int cbx_step_and_synchronise(cbx_context *c, int first, int clock, int autotune, const int *tasks, void *const *streams,
-                             unsigned flags) {
-  TraceRange trace("cbx_step_and_synchronise");
-  const char *me = "cbx_step_and_synchronise";
+// `variables`: cbx_step_and_synchronise_variables, which honours the
+// per-variable rates (task_barrier_variables_kernels.hip) where the plain
+// call refuses them; everything else is one code path.
+static int step_and_synchronise(cbx_context *c, int first, int clock, int autotune, const int *tasks,
+                                void *const *streams, unsigned flags, bool variables) {
+  const char *me = variables ? "cbx_step_and_synchronise_variables" : "cbx_step_and_synchronise";
+  TraceRange trace(me);
   TRY(check_manager_q(c));
   if (first < 0 || first > c->size) return fail(CBX_ERR_INVALID, "first replica %d out of range", first);
   if (!tasks) return fail(CBX_ERR_INVALID, "%s: null task list (one entry per replica: a task number, or -1)", me);
@@ -710,10 +726,15 @@ int cbx_step_and_synchronise(cbx_context *c, int first, int clock, int autotune,
   if (c->clip_on())
     return fail(CBX_ERR_UNSUPPORTED, "%s: gradient clipping is on; the clipped step needs its norm pass first, use "
                 "cbx_replica_optimise and cbx_synchronise", me);
-  if (c->variable_rates && c->model.conf.irregular > 0)
+  const bool per_variable = c->variable_rates && c->model.conf.irregular > 0;
+  if (per_variable && !variables)
     return fail(CBX_ERR_UNSUPPORTED, "%s: variable learning rates are on with %d irregular variables; use "
                 "cbx_replica_optimise and cbx_synchronise", me, c->model.conf.irregular);
+  if (per_variable && !c->var_refusal.empty())
+    return fail(CBX_ERR_UNSUPPORTED, "%s with variable learning rates: %s", me, c->var_refusal.c_str());
   Device &d = c->devs[0];
+  if (per_variable && !d.var_tables_padded.chunks)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: the padded model is too large for the chunk table", me);
   const SolverConf *ref = nullptr;  // the first stepping replica's configuration
   int participating = 0;
   for (int id : d.replicas) {
@@ -789,11 +810,23 @@ int cbx_step_and_synchronise(cbx_context *c, int first, int clock, int autotune,
 
   cbx::LaunchConfig cfg = c->task_barrier_cfg;
   cfg.num_cus = d.num_cus;
-  HIP_TRY(cbx::launch_task_barrier(a, (flags & CBX_STEP_DISCARD_TASK_OUTPUTS) == 0, cfg, d.stream,
-                                   {step_start_event(c, d, 0), step_stop_event(c, d, EV_A)}));
+  const bool keep = (flags & CBX_STEP_DISCARD_TASK_OUTPUTS) == 0;
+  const cbx::Timing tm = {step_start_event(c, d, 0), step_stop_event(c, d, EV_A)};
+  if (per_variable) HIP_TRY(cbx::launch_task_barrier_variables(a, d.var_tables_padded, keep, cfg, d.stream, tm));
+  else HIP_TRY(cbx::launch_task_barrier(a, keep, cfg, d.stream, tm));
   close_fused_step(c, d);
   TRY(finish_sma_step(c, first));
   return finish_barrier(c, clock, autotune);
+}
+
+int cbx_step_and_synchronise(cbx_context *c, int first, int clock, int autotune, const int *tasks, void *const *streams,
+                             unsigned flags) {
+  return step_and_synchronise(c, first, clock, autotune, tasks, streams, flags, false);
+}
+
+int cbx_step_and_synchronise_variables(cbx_context *c, int first, int clock, int autotune, const int *tasks,
+                                       void *const *streams, unsigned flags) {
+  return step_and_synchronise(c, first, clock, autotune, tasks, streams, flags, true);
 }
 
 int cbx_unlock_any(cbx_context *c) {

@@ -398,6 +398,9 @@ struct Device {
   size_t bn_scratch_bytes = 0;
   cbx::StatsScratch stats;             // cbx_model_stats: piece table, slab, results
   cbx::VarTables var_tables;           // the per-variable replica step: chunk table, bounds, multipliers
+  // cbx_step_and_synchronise_variables: the same tables over the padded length,
+  // the pad a last pseudo-variable of multiplier 1 (build_padded_optimise_plan)
+  cbx::VarTables var_tables_padded;
   int num_cus = 256;
   // Arena: [base data][base gradient(ctrl+acc)][base diff(ctrl+D)][base last]
   //        then per replica [data][diff][last][gradient].
@@ -875,6 +878,7 @@ inline void close_device(Device &d) {
   if (d.bn_scratch) (void)hipFree(d.bn_scratch);
   cbx::stats_free(d.stats);
   cbx::var_tables_free(d.var_tables);
+  cbx::var_tables_free(d.var_tables_padded);
   if (d.host) (void)hipHostFree(d.host);
   if (d.synched) (void)hipEventDestroy(d.synched);
   for (int k = 0; k < EV_COUNT; ++k)

@@ -80,4 +80,24 @@ inline bool build_optimise_plan(const long long *var_elements, int nvars, long l
   return true;
 }
 
+// The table of a buffer padded to `padded_elements` >= elements floats (the
+// context's buffers, whole kPadFloat4s): the pad floats belong to a last
+// pseudo-variable, index nvars, which the caller gives the multiplier 1, so a
+// kernel that sweeps the padded length (task_barrier_variables_kernels.hip)
+// reads no table past its end and steps a zero pad to zero.  The floats
+// [0, elements) keep their own variables: a last partial chunk becomes a mixed
+// chunk.  out->nvars is nvars + 1, out->elements the padded length; with no
+// pad the pseudo-variable has no floats and no chunk names it.
+inline bool build_padded_optimise_plan(const long long *var_elements, int nvars, long long elements,
+                                       long long padded_elements, OptimisePlan *out) {
+  OptimisePlan plain;
+  if (padded_elements < elements || !build_optimise_plan(var_elements, nvars, elements, &plain)) {
+    build_optimise_plan(nullptr, 0, 0, out);  // clears *out
+    return false;
+  }
+  std::vector<long long> v(var_elements, var_elements + nvars);
+  v.push_back(padded_elements - elements);
+  return build_optimise_plan(v.data(), nvars + 1, padded_elements, out);
+}
+
 }  // namespace cbx

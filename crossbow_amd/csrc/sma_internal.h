@@ -372,6 +372,16 @@ struct TaskBarrierArgs {
 // is no whole number of 64 x unroll chunks (the context's always is).
 hipError_t launch_task_barrier(const TaskBarrierArgs &a, bool keep_task_outputs, const LaunchConfig &cfg,
                                hipStream_t stream, Timing t = {});
+// The same launch with a learning rate per variable
+// (task_barrier_variables_kernels.hip, a shared object of its own:
+// libcrossbow_sma_variables.so): stepping replica k steps variable v with
+// a.rate[k] * t.mult[v], one fp32 multiply, and otherwise launch_task_barrier's
+// sequence.  `t` covers at least a.n4 * 4 floats in whole chunks (the context's
+// table is built over the padded length, build_padded_optimise_plan) and
+// a.tail_hi.  Compiled forms: no tail with unroll 1 or 2 and either policy; a
+// tail with unroll 1 and policy 1.  Anything else is hipErrorInvalidValue.
+hipError_t launch_task_barrier_variables(const TaskBarrierArgs &a, const VarTables &t, bool keep_task_outputs,
+                                         const LaunchConfig &cfg, hipStream_t stream, Timing tm = {});
 // One-wave blocks, one float4 per lane, auto occupancy (2 waves per CU at
 // R = 8): at the SMA step's own shape, two float4s per lane, it measured 2-5 %
 // slower in each of three runs (scripts/bench_step_and_synchronise.py --sweep,

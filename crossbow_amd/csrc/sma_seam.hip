@@ -494,14 +494,18 @@ int cbx_sma_plan_step(cbx_sma_plan *p, void *const *streams, float *const *z, fl
 // not fused.  The bulk runs the context's float4 loop, the elements past it the
 // kernel's TAIL workgroups (task_barrier_kernels.hip).  Everything is
 // validated before the launch; the plan queues no wait of its own.
-int cbx_sma_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *const *z, float *const *last,
-                                   int nreplicas, const int *replica_device, float *const *w, float *const *s,
-                                   float *const *g, float *const *rlast, const int *locked, const int *copy,
-                                   const int *step, const float *learning_rate, float alpha, float momentum,
-                                   float replica_momentum, float weight_decay, int first, unsigned flags) {
-  TraceRange trace("cbx_sma_plan_step_and_optimise");
-  const char *me = "cbx_sma_plan_step_and_optimise";
+// `variables`: cbx_sma_plan_step_and_optimise_variables, the same call over the
+// plan's variable table (task_barrier_variables_kernels.hip).
+static int plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *const *z, float *const *last,
+                                  int nreplicas, const int *replica_device, float *const *w, float *const *s,
+                                  float *const *g, float *const *rlast, const int *locked, const int *copy,
+                                  const int *step, const float *learning_rate, float alpha, float momentum,
+                                  float replica_momentum, float weight_decay, int first, unsigned flags,
+                                  bool variables) {
+  const char *me = variables ? "cbx_sma_plan_step_and_optimise_variables" : "cbx_sma_plan_step_and_optimise";
+  TraceRange trace(me);
   if (!p) return fail(CBX_ERR_INVALID, "null plan");
+  if (variables && p->var_bounds.empty()) return fail(CBX_ERR_STATE, "%s before cbx_sma_plan_set_variables", me);
   if (!streams || !z || nreplicas < 0 ||
       (nreplicas > 0 && (!replica_device || !w || !s || !g || !locked || !copy || !step || !learning_rate)))
     return fail(CBX_ERR_INVALID, "%s: missing arguments", me);
@@ -567,8 +571,31 @@ int cbx_sma_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float 
   HIP_TRY(hipSetDevice(d.hip_id));
   cbx::LaunchConfig cfg = p->task_barrier_cfg;
   cfg.num_cus = d.num_cus;
-  HIP_TRY(cbx::launch_task_barrier(a, keep, cfg, static_cast<hipStream_t>(streams[0]), p->next_timing()));
+  if (variables)
+    HIP_TRY(cbx::launch_task_barrier_variables(a, d.var_tables, keep, cfg, static_cast<hipStream_t>(streams[0]),
+                                               p->next_timing()));
+  else
+    HIP_TRY(cbx::launch_task_barrier(a, keep, cfg, static_cast<hipStream_t>(streams[0]), p->next_timing()));
   return copies > 0 ? 1 : 0;
+}
+
+int cbx_sma_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *const *z, float *const *last,
+                                   int nreplicas, const int *replica_device, float *const *w, float *const *s,
+                                   float *const *g, float *const *rlast, const int *locked, const int *copy,
+                                   const int *step, const float *learning_rate, float alpha, float momentum,
+                                   float replica_momentum, float weight_decay, int first, unsigned flags) {
+  return plan_step_and_optimise(p, streams, z, last, nreplicas, replica_device, w, s, g, rlast, locked, copy, step,
+                                learning_rate, alpha, momentum, replica_momentum, weight_decay, first, flags, false);
+}
+
+int cbx_sma_plan_step_and_optimise_variables(cbx_sma_plan *p, void *const *streams, float *const *z,
+                                             float *const *last, int nreplicas, const int *replica_device,
+                                             float *const *w, float *const *s, float *const *g, float *const *rlast,
+                                             const int *locked, const int *copy, const int *step,
+                                             const float *learning_rate, float alpha, float momentum,
+                                             float replica_momentum, float weight_decay, int first, unsigned flags) {
+  return plan_step_and_optimise(p, streams, z, last, nreplicas, replica_device, w, s, g, rlast, locked, copy, step,
+                                learning_rate, alpha, momentum, replica_momentum, weight_decay, first, flags, true);
 }
 
 // crossbowSynchronisationSynchronousSGD (synch/synchronoussgd.c:13-106) over

@@ -91,14 +91,29 @@ class SmaPlan:
         ``STEP_DISCARD_TASK_OUTPUTS``, under which a stepping replica's ``s``
         may be None.  The caller orders ``streams[0]`` behind the gradients.
         Returns 1 when Phase D ran."""
+        return self._step_and_optimise("cbx_sma_plan_step_and_optimise", streams, z, last, replicas, alpha, momentum,
+                                       replica_momentum, weight_decay, first, flags)
+
+    def step_and_optimise_variables(self, streams, z, last, replicas, alpha: float, momentum: float,
+                                    replica_momentum: float, weight_decay: float, first: int = 0,
+                                    flags: int = 0) -> int:
+        """``step_and_optimise`` with a learning rate per variable
+        (``cbx_sma_plan_step_and_optimise_variables``): variable v of a
+        stepping replica steps at ``learning_rate * multipliers[v]`` of the
+        table ``set_variables`` installed.  Same arguments."""
+        return self._step_and_optimise("cbx_sma_plan_step_and_optimise_variables", streams, z, last, replicas, alpha,
+                                       momentum, replica_momentum, weight_decay, first, flags)
+
+    def _step_and_optimise(self, name, streams, z, last, replicas, alpha, momentum, replica_momentum, weight_decay,
+                           first, flags) -> int:
         rate = (ctypes.c_float * max(1, len(replicas)))(*[float(r[8]) for r in replicas])
-        return _raise(self.lib, self.lib.cbx_sma_plan_step_and_optimise(
+        return _raise(self.lib, getattr(self.lib, name)(
             self._p, _ptrs(streams), _ptrs(z), _ptrs(last) if last is not None else None, len(replicas),
             _ints([r[0] for r in replicas]), _ptrs([r[1] for r in replicas]), _ptrs([r[2] for r in replicas]),
             _ptrs([r[3] for r in replicas]), _ptrs([r[4] for r in replicas]), _ints([r[5] for r in replicas]),
             _ints([r[6] for r in replicas]), _ints([r[7] for r in replicas]), rate, ctypes.c_float(alpha),
             ctypes.c_float(momentum), ctypes.c_float(replica_momentum), ctypes.c_float(weight_decay), first,
-            ctypes.c_uint(flags)), "cbx_sma_plan_step_and_optimise")
+            ctypes.c_uint(flags)), name)
 
     def ssgd_step(self, streams: Sequence[int], z: Sequence[int], last: Optional[Sequence[Optional[int]]],
                   acc: Sequence[int], replicas: Sequence[Tuple[int, int, int]], momentum: float, wpc: int,

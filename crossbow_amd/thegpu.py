@@ -210,6 +210,19 @@ class TheGPU:
         on (None: the sync stream).  ``flags`` may be
         ``STEP_DISCARD_TASK_OUTPUTS`` (include/crossbow_sma.h has the promise
         that goes with it)."""
+        return self._step_and_synchronise(self._L.cbx_step_and_synchronise, first, clock, autotune, tasks, streams,
+                                          flags)
+
+    def step_and_synchronise_variables(self, first: int, clock: int, autotune: int, tasks: Sequence[int],
+                                       streams: Optional[Sequence[Optional[int]]] = None, flags: int = 0) -> int:
+        """``cbx_step_and_synchronise_variables``: ``step_and_synchronise`` for
+        a model with per-variable learning rates (``setVariableLearningRates``
+        on and a multiplier that is not 1), which that call refuses.  Same
+        arguments; without such rates it is that call."""
+        return self._step_and_synchronise(self._L.cbx_step_and_synchronise_variables, first, clock, autotune, tasks,
+                                          streams, flags)
+
+    def _step_and_synchronise(self, fn, first, clock, autotune, tasks, streams, flags) -> int:
         tasks = list(tasks)
         N = self.num_replicas()
         if len(tasks) != N:
@@ -221,7 +234,7 @@ class TheGPU:
             if len(streams) != N:
                 raise ValueError(f"one stream entry per replica ({N}) expected, got {len(streams)}")
             sa = (ctypes.c_void_p * max(1, N))(*[s if s else None for s in streams])
-        return check(self._L.cbx_step_and_synchronise(self._ctx, first, clock, autotune, ta, sa, flags))
+        return check(fn(self._ctx, first, clock, autotune, ta, sa, flags))
 
     def unlockAny(self) -> int:
         return check(self._L.cbx_unlock_any(self._ctx))

@@ -242,10 +242,41 @@ int cbx_synchronise_staged (cbx_context *ctx, int first, int clock, int autotune
  * (7) or SYNCHRONOUSEAMSGD (3) without elastic averaging; gradient clipping on;
  * cbx_set_variable_learning_rates on with a multiplier that is not 1; Nesterov
  * momentum on a stepping replica; stepping replicas whose momentum or weight
- * decay differ.  CBX_ERR_STATE: replica momentum without a `last` buffer.   */
+ * decay differ.  CBX_ERR_STATE: replica momentum without a `last` buffer.
+ * A model with per-variable rates takes cbx_step_and_synchronise_variables
+ * below; this call keeps its refusal.                                      */
 #define CBX_STEP_DISCARD_TASK_OUTPUTS 1u
 int cbx_step_and_synchronise (cbx_context *ctx, int first, int clock, int autotune,
                               const int *tasks, void *const *streams, unsigned flags);
+/* cbx_step_and_synchronise for a model with per-variable learning rates
+ * (cbx_set_variable_learning_rates on and a multiplier that is not 1; the
+ * reference's crossbowModelGetLearningRateForVariable, model.c:159-177, which
+ * every optimiser of the reference honours).  Same parameters, same checks and
+ * refusals in the same order and before the first side effect, except that
+ * variable rates are honoured, not refused; gradient clipping stays
+ * CBX_ERR_UNSUPPORTED.  A model whose variables do not tile its elements is
+ * CBX_ERR_UNSUPPORTED with the reason cbx_replica_optimise gives.
+ *
+ * The arithmetic.  Per element of variable v and per stepping replica i
+ *   r_iv = rate_i * mult[v],  rate_i = -lr_i  (one fp32 multiply, as in
+ *                                              cbx_replica_optimise)
+ * and then cbx_step_and_synchronise's sequence with r_iv in place of rate_i.
+ * A replica that only joins, the base momentum, Phase D and
+ * CBX_STEP_DISCARD_TASK_OUTPUTS are as in that call.
+ *
+ * The contract.  With flags == 0 every buffer and every piece of host state is
+ * left bit for bit as after
+ *   cbx_replica_optimise (ctx, id, tasks[id], streams[id])  (variable rates on)
+ *                                     for every id with tasks[id] >= 0, in id order,
+ *   cbx_synchronise (ctx, first, clock, autotune, 0).
+ * With the discard flag, s_i and g_i of the stepping replicas keep what they
+ * held.  The pad floats behind the model's elements step as a pseudo-variable
+ * of multiplier 1: a zero pad stays zero.
+ *
+ * With cbx_set_variable_learning_rates off, or every multiplier 1, the call is
+ * cbx_step_and_synchronise: the same kernel, the same bits.                */
+int cbx_step_and_synchronise_variables (cbx_context *ctx, int first, int clock, int autotune,
+                                        const int *tasks, void *const *streams, unsigned flags);
 /* TheGPU.unlockAny() GPU.c:1142-1149 -> modelmanager.c:233-245           */
 int cbx_unlock_any (cbx_context *ctx);
 
@@ -932,6 +963,28 @@ int cbx_sma_plan_step_and_optimise (cbx_sma_plan *plan, void *const *streams,
                                     const float *learning_rate,
                                     float alpha, float momentum, float replica_momentum, float weight_decay,
                                     int first, unsigned flags);
+/* cbx_sma_plan_step_and_optimise with a learning rate per variable: stepping
+ * replica id steps variable v with r = (-learning_rate[id]) * multipliers[v],
+ * one fp32 multiply, over the table that cbx_sma_plan_set_variables installed
+ * (CBX_ERR_STATE without one).  Parameters, checks and refusals are those of
+ * cbx_sma_plan_step_and_optimise.  With flags == 0 every buffer is left bit
+ * for bit as after
+ *   cbx_sma_plan_optimise_variables (plan, 0, streams[0], w[id], g[id], rlast[id],
+ *       s[id], learning_rate[id], replica_momentum, weight_decay, 0, all variables)
+ *                                 for every id with step[id] != 0, in id order,
+ *   cbx_sma_plan_step (plan, streams, z, last, nreplicas, replica_device, w, s,
+ *       locked, copy, alpha, momentum, first);
+ * with CBX_STEP_DISCARD_TASK_OUTPUTS, s[id] and g[id] of the stepping replicas
+ * are not written.  Nothing at or past `elements` is read or written.       */
+int cbx_sma_plan_step_and_optimise_variables (cbx_sma_plan *plan, void *const *streams,
+                                              float *const *z, float *const *last,
+                                              int nreplicas, const int *replica_device,
+                                              float *const *w, float *const *s, float *const *g,
+                                              float *const *rlast,
+                                              const int *locked, const int *copy, const int *step,
+                                              const float *learning_rate,
+                                              float alpha, float momentum, float replica_momentum,
+                                              float weight_decay, int first, unsigned flags);
 /* The statistics reduction of cbx_model_stats over caller-owned buffers of
  * exactly the plan's `elements` floats on the plan's device k (where a
  * Crossbow build would checksum, databuffer.c:141-162): `ref` against
