@@ -9,6 +9,9 @@
   with a learning rate per variable (csrc/task_barrier_variables_kernels.hip):
   a shared object of its own, built first, so the device code of
   ``libcrossbow_sma.so`` (``code_object_digest``) stays what it was.
+* ``crossbow_amd/libcrossbow_sma_clipped.so`` -- the fused task-step barrier
+  with gradient clipping (csrc/task_barrier_clipped_kernels.hip): likewise a
+  shared object of its own, built first and linked by the library.
 * ``crossbow_amd/libGPU.so``           -- the JNI shim exporting Crossbow's
   ``TheGPU`` model-path natives; built only where ``jni.h`` exists (there is
   no JDK in this image).
@@ -28,6 +31,7 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libcrossbow_sma.so")
 VARIABLES_LIB = os.path.join(PKG, "libcrossbow_sma_variables.so")
+CLIPPED_LIB = os.path.join(PKG, "libcrossbow_sma_clipped.so")
 JNI_LIB = os.path.join(PKG, "libGPU.so")
 ARCH = "gfx950"
 
@@ -42,6 +46,7 @@ def _hipcc() -> str:
 SOURCES = ("context.hip", "sync_steps.hip", "sma_kernels.hip", "averaging_kernels.hip", "sma_seam.hip",
            "stats_kernels.hip", "variable_rate_kernels.hip", "clip_kernels.hip", "task_barrier_kernels.hip")
 VARIABLES_SOURCES = ("task_barrier_variables_kernels.hip",)
+CLIPPED_SOURCES = ("task_barrier_clipped_kernels.hip",)
 HEADERS = ("context_internal.h", "sma_internal.h", "stream_helpers.h", "stats_internal.h", "stats_plan.h",
            "optimise_plan.h", "clip_internal.h", "bucket_pipeline.h")
 
@@ -51,8 +56,9 @@ def _sources(names=SOURCES):
 
 
 def _deps():
-    return _sources() + _sources(VARIABLES_SOURCES) + [os.path.join(CSRC, f) for f in HEADERS] + [os.path.join(ROOT, "include", "crossbow_sma.h"),
-                                                                   os.path.abspath(__file__)]
+    return (_sources() + _sources(VARIABLES_SOURCES) + _sources(CLIPPED_SOURCES) +
+            [os.path.join(CSRC, f) for f in HEADERS] + [os.path.join(ROOT, "include", "crossbow_sma.h"),
+                                                        os.path.abspath(__file__)])
 
 
 def _stale(target: str, deps) -> bool:
@@ -93,15 +99,16 @@ def _link(target, objs, libs, verbose):
 
 
 def build_lib(force: bool = False, verbose: bool = False) -> str:
-    # one staleness check for both libraries: they share the headers
-    if not force and not _stale(LIB, _deps()) and not _stale(VARIABLES_LIB, _deps()):
+    # one staleness check for all three libraries: they share the headers
+    if not force and not any(_stale(t, _deps()) for t in (LIB, VARIABLES_LIB, CLIPPED_LIB)):
         return LIB
     objdir = os.path.join(PKG, "build")
     os.makedirs(objdir, exist_ok=True)
-    # the object of the per-variable fused barrier first: the library links against it
+    # the objects of the per-variable and the clipped fused barrier first: the library links against them
     _link(VARIABLES_LIB, _compile(_sources(VARIABLES_SOURCES), objdir, verbose), [], verbose)
+    _link(CLIPPED_LIB, _compile(_sources(CLIPPED_SOURCES), objdir, verbose), [], verbose)
     _link(LIB, _compile(_sources(), objdir, verbose),
-          ["-L", PKG, "-lcrossbow_sma_variables", "-Wl,-rpath,$ORIGIN", "-lrccl", "-lrocprofiler-sdk-roctx", "-lpthread"],
+          ["-L", PKG, "-lcrossbow_sma_variables", "-lcrossbow_sma_clipped", "-Wl,-rpath,$ORIGIN", "-lrccl", "-lrocprofiler-sdk-roctx", "-lpthread"],
           verbose)
     return LIB
 

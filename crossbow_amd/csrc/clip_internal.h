@@ -75,4 +75,22 @@ hipError_t launch_sma_optimise_clipped(const OptArgs &a, const ClipRecord *rec, 
 hipError_t launch_sma_optimise_variables_clipped(const VarTables &t, VarOptArgs a, const ClipRecord *rec,
                                                  const LaunchConfig &cfg, hipStream_t stream, Timing tm = {});
 
+// The records of a fused launch's participating replicas, in TaskBarrierArgs'
+// order: a kernel parameter of its own (512 bytes) beside that block.
+struct ClipRecordPtrs {
+  const ClipRecord *__restrict__ p[kMaxReplicas];
+};
+// launch_task_barrier with the clipped step (task_barrier_clipped_kernels.hip,
+// a shared object of its own: libcrossbow_sma_clipped.so): stepping replica k
+// multiplies g by the scale of rec.p[k] before weight decay, writes a kept g
+// always, and with the record's skip bit does s = w and nothing else before it
+// joins the barrier.  rec.p[k] is the record launch_gradient_norm left earlier
+// on the stream, non-null for every stepping replica; the other entries are not
+// read.  At least one replica steps (without one there is nothing to clip:
+// launch_task_barrier).  Compiled forms: no tail with unroll 1 or 2 and either
+// policy; a tail with unroll 1 and policy 1.  Anything else is
+// hipErrorInvalidValue, before the launch.
+hipError_t launch_task_barrier_clipped(const TaskBarrierArgs &a, const ClipRecordPtrs &rec, bool keep_task_outputs,
+                                       const LaunchConfig &cfg, hipStream_t stream, Timing t = {});
+
 }  // namespace cbx

@@ -692,12 +692,20 @@ int cbx_synchronise_staged(cbx_context *c, int first, int clock, int autotune, i
 // The pending task steps of the locked replicas and the one-GPU SMA barrier in
 // one launch (task_barrier_kernels.hip).  Everything is validated before the
 // first side effect: a refused call leaves buffers, flags and clocks alone.
-// `variables`: cbx_step_and_synchronise_variables, which honours the
+// FusedVariables: cbx_step_and_synchronise_variables, which honours the
 // per-variable rates (task_barrier_variables_kernels.hip) where the plain
-// call refuses them; everything else is one code path.
+// call refuses them.  FusedClipped: cbx_step_and_synchronise_clipped, which
+// runs every stepping replica's norm pass in front of the launch and the
+// clipped step inside it (task_barrier_clipped_kernels.hip) where the plain
+// call refuses clipping.  Everything else is one code path.
+enum FusedMode { FusedPlain, FusedVariables, FusedClipped };
+
 static int step_and_synchronise(cbx_context *c, int first, int clock, int autotune, const int *tasks,
-                                void *const *streams, unsigned flags, bool variables) {
-  const char *me = variables ? "cbx_step_and_synchronise_variables" : "cbx_step_and_synchronise";
+                                void *const *streams, unsigned flags, FusedMode mode) {
+  const bool variables = mode == FusedVariables;
+  const char *me = mode == FusedClipped ? "cbx_step_and_synchronise_clipped"
+                   : variables          ? "cbx_step_and_synchronise_variables"
+                                        : "cbx_step_and_synchronise";
   TraceRange trace(me);
   TRY(check_manager_q(c));
   if (first < 0 || first > c->size) return fail(CBX_ERR_INVALID, "first replica %d out of range", first);
@@ -723,13 +731,15 @@ static int step_and_synchronise(cbx_context *c, int first, int clock, int autotu
     return fail(CBX_ERR_UNSUPPORTED, "%s: elastic averaging is on (cbx_set_elastic_average); only the SMA barrier is fused", me);
   if (type != CBX_UPDATE_SMA && type != CBX_UPDATE_SYNCHRONOUSEAMSGD)
     return fail(CBX_ERR_UNSUPPORTED, "%s: update model %d; only SMA (7) and SYNCHRONOUSEAMSGD (3) are fused", me, type);
-  if (c->clip_on())
+  const bool clip = c->clip_on();
+  if (clip && mode != FusedClipped)
     return fail(CBX_ERR_UNSUPPORTED, "%s: gradient clipping is on; the clipped step needs its norm pass first, use "
                 "cbx_replica_optimise and cbx_synchronise", me);
   const bool per_variable = c->variable_rates && c->model.conf.irregular > 0;
   if (per_variable && !variables)
-    return fail(CBX_ERR_UNSUPPORTED, "%s: variable learning rates are on with %d irregular variables; use "
-                "cbx_replica_optimise and cbx_synchronise", me, c->model.conf.irregular);
+    return fail(CBX_ERR_UNSUPPORTED, "%s: variable learning rates are on with %d irregular variables; %suse "
+                "cbx_replica_optimise and cbx_synchronise", me, c->model.conf.irregular,
+                mode == FusedClipped ? "the clipped step with a rate per variable is not fused, " : "");
   if (per_variable && !c->var_refusal.empty())
     return fail(CBX_ERR_UNSUPPORTED, "%s with variable learning rates: %s", me, c->var_refusal.c_str());
   Device &d = c->devs[0];
@@ -755,6 +765,7 @@ static int step_and_synchronise(cbx_context *c, int first, int clock, int autotu
     if (conf.policy == LR_CLR) return fail(CBX_ERR_UNSUPPORTED, "circular learning rate is unsupported");
     if (conf.policy < LR_FIXED || conf.policy > LR_LSR)
       return fail(CBX_ERR_UNSUPPORTED, "learning-rate policy %d unsupported", (int)conf.policy);
+    if (clip && !c->replicas[id]->clip.dev) return fail(CBX_ERR_STATE, "replica %d has no gradient-clip scratch", id);
   }
   if (participating > cbx::kMaxReplicas)
     return fail(CBX_ERR_UNSUPPORTED, "more than %d locked replicas on one device", cbx::kMaxReplicas);
@@ -769,8 +780,15 @@ static int step_and_synchronise(cbx_context *c, int first, int clock, int autotu
 
   cbx::TaskBarrierArgs a;
   std::memset(&a, 0, sizeof(a));
+  cbx::ClipRecordPtrs records;
+  std::memset(&records, 0, sizeof(records));
   int k = 0, copies = 0;
   std::vector<hipStream_t> callers;
+  struct Norm {
+    Replica *r;
+    hipStream_t st;
+  };
+  std::vector<Norm> norms;  // the stepping replicas of a clipped call, id order
   for (int id : d.replicas) {  // increasing id order, sma.c:69
     if (id < first || !c->locked[id]) continue;
     Replica &r = *c->replicas[id];
@@ -783,6 +801,10 @@ static int step_and_synchronise(cbx_context *c, int first, int clock, int autotu
       a.rate[k] = -lr[(size_t)id];  // sma.cu:43
       hipStream_t st = streams && streams[id] ? reinterpret_cast<hipStream_t>(streams[id]) : d.stream;
       if (st != d.stream && std::find(callers.begin(), callers.end(), st) == callers.end()) callers.push_back(st);
+      if (clip) {
+        records.p[k] = r.clip.record();
+        norms.push_back({&r, st});
+      }
     }
     if (r.conf.copy) copies++;  // sma.c:113-120, after the queries
     ++k;
@@ -800,6 +822,21 @@ static int step_and_synchronise(cbx_context *c, int first, int clock, int autotu
   // The launch comes after the gradients: one deferred wait per caller stream,
   // queued now, as cbx_synchronise queues the task steps' (DESIGN.md 7).
   HIP_TRY(hipSetDevice(d.hip_id));
+  // The clipped call's norm passes, where cbx_replica_optimise puts them: on
+  // the replica's stream, behind the last barrier's use of the replica and its
+  // record, and in front of that stream's deferred wait, which then orders the
+  // launch behind them.  A pass on the sync stream comes after the updates made
+  // on other streams.  S, K, the scale, the flags and the counts are the
+  // sequence's bits: it is the sequence's code (launch_gradient_norm).
+  if (!norms.empty()) {
+    if (std::any_of(norms.begin(), norms.end(), [&](const Norm &nm) { return nm.st == d.stream; }))
+      TRY(flush_task_waits(c));
+    for (const Norm &nm : norms) {
+      if (nm.st != d.stream && d.step_event) HIP_TRY(hipStreamWaitEvent(nm.st, d.step_event, 0));
+      HIP_TRY(cbx::launch_gradient_norm(replica_dev(d, *nm.r, CBX_BUF_GRADIENT), c->n, nm.r->clip, c->clip_max_norm,
+                                        c->clip_skip_nonfinite, c->clip_norm_policy, nm.st));
+    }
+  }
   if (!c->fault_skip_task_wait)
     for (hipStream_t st : callers) TRY(defer_task_wait(d, st));
   TRY(flush_task_waits(c));
@@ -812,7 +849,9 @@ static int step_and_synchronise(cbx_context *c, int first, int clock, int autotu
   cfg.num_cus = d.num_cus;
   const bool keep = (flags & CBX_STEP_DISCARD_TASK_OUTPUTS) == 0;
   const cbx::Timing tm = {step_start_event(c, d, 0), step_stop_event(c, d, EV_A)};
+  // a clipped call in which no replica steps has nothing to clip: the plain kernel, the same bits
   if (per_variable) HIP_TRY(cbx::launch_task_barrier_variables(a, d.var_tables_padded, keep, cfg, d.stream, tm));
+  else if (!norms.empty()) HIP_TRY(cbx::launch_task_barrier_clipped(a, records, keep, cfg, d.stream, tm));
   else HIP_TRY(cbx::launch_task_barrier(a, keep, cfg, d.stream, tm));
   close_fused_step(c, d);
   TRY(finish_sma_step(c, first));
@@ -821,12 +860,17 @@ static int step_and_synchronise(cbx_context *c, int first, int clock, int autotu
 
 int cbx_step_and_synchronise(cbx_context *c, int first, int clock, int autotune, const int *tasks, void *const *streams,
                              unsigned flags) {
-  return step_and_synchronise(c, first, clock, autotune, tasks, streams, flags, false);
+  return step_and_synchronise(c, first, clock, autotune, tasks, streams, flags, FusedPlain);
 }
 
 int cbx_step_and_synchronise_variables(cbx_context *c, int first, int clock, int autotune, const int *tasks,
                                        void *const *streams, unsigned flags) {
-  return step_and_synchronise(c, first, clock, autotune, tasks, streams, flags, true);
+  return step_and_synchronise(c, first, clock, autotune, tasks, streams, flags, FusedVariables);
+}
+
+int cbx_step_and_synchronise_clipped(cbx_context *c, int first, int clock, int autotune, const int *tasks,
+                                     void *const *streams, unsigned flags) {
+  return step_and_synchronise(c, first, clock, autotune, tasks, streams, flags, FusedClipped);
 }
 
 int cbx_unlock_any(cbx_context *c) {

@@ -494,18 +494,38 @@ int cbx_sma_plan_step(cbx_sma_plan *p, void *const *streams, float *const *z, fl
 // not fused.  The bulk runs the context's float4 loop, the elements past it the
 // kernel's TAIL workgroups (task_barrier_kernels.hip).  Everything is
 // validated before the launch; the plan queues no wait of its own.
-// `variables`: cbx_sma_plan_step_and_optimise_variables, the same call over the
-// plan's variable table (task_barrier_variables_kernels.hip).
+// SeamVariables: cbx_sma_plan_step_and_optimise_variables, the same call over the
+// plan's variable table (task_barrier_variables_kernels.hip).  SeamClipped:
+// cbx_sma_plan_step_and_optimise_clipped, with every stepping replica's norm
+// pass over its slot's scratch on streams[0] in front of the launch and the
+// clipped step inside it (task_barrier_clipped_kernels.hip).
+namespace {
+int clip_slot(cbx_sma_plan *p, const char *what, int k, int slot, cbx::ClipScratch **out);
+enum SeamMode { SeamPlain, SeamVariables, SeamClipped };
+struct SeamClip {
+  const int *slot = nullptr;
+  float max_norm = 0.0f;
+  int skip_nonfinite = 0;
+};
+}  // namespace
+
 static int plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *const *z, float *const *last,
                                   int nreplicas, const int *replica_device, float *const *w, float *const *s,
                                   float *const *g, float *const *rlast, const int *locked, const int *copy,
                                   const int *step, const float *learning_rate, float alpha, float momentum,
                                   float replica_momentum, float weight_decay, int first, unsigned flags,
-                                  bool variables) {
-  const char *me = variables ? "cbx_sma_plan_step_and_optimise_variables" : "cbx_sma_plan_step_and_optimise";
+                                  SeamMode mode, const SeamClip &clip = SeamClip()) {
+  const bool variables = mode == SeamVariables, clipped = mode == SeamClipped;
+  const char *me = clipped     ? "cbx_sma_plan_step_and_optimise_clipped"
+                   : variables ? "cbx_sma_plan_step_and_optimise_variables"
+                               : "cbx_sma_plan_step_and_optimise";
   TraceRange trace(me);
   if (!p) return fail(CBX_ERR_INVALID, "null plan");
   if (variables && p->var_bounds.empty()) return fail(CBX_ERR_STATE, "%s before cbx_sma_plan_set_variables", me);
+  if (clipped && (!(clip.max_norm >= 0.0f) || std::isinf(clip.max_norm)))
+    return fail(CBX_ERR_INVALID, "%s: max_norm %g is negative, NaN or infinite", me, (double)clip.max_norm);
+  if (clipped && clip.skip_nonfinite != 0 && clip.skip_nonfinite != 1)
+    return fail(CBX_ERR_INVALID, "%s: skip_nonfinite %d is neither 0 nor 1", me, clip.skip_nonfinite);
   if (!streams || !z || nreplicas < 0 ||
       (nreplicas > 0 && (!replica_device || !w || !s || !g || !locked || !copy || !step || !learning_rate)))
     return fail(CBX_ERR_INVALID, "%s: missing arguments", me);
@@ -530,6 +550,9 @@ static int plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *
   std::memset(&a, 0, sizeof(a));
   int copies = 0, participating = 0;
   bool steps = false;
+  int slot_of[cbx::kMaxReplicas];  // clipped: the slot of participating replica k, or -1
+  uint64_t slots_taken = 0;
+  static_assert(cbx_sma_plan::kClipSlots <= 64, "one bit per slot");
   for (int id = first; id < nreplicas; ++id) {  // increasing id order, sma.c:69
     if (!locked[id]) continue;
     if (replica_device[id] != 0) return fail(CBX_ERR_INVALID, "%s: replica %d on device %d of 1", me, id, replica_device[id]);
@@ -542,8 +565,19 @@ static int plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *
       return fail(CBX_ERR_INVALID, "%s: stepping replica %d: g must be non-null and 16-byte aligned", me, id);
     if (st && rmom && (!rlast[id] || !aligned16(rlast[id])))
       return fail(CBX_ERR_INVALID, "%s: stepping replica %d: replica momentum > 0 needs a 16-byte aligned last buffer", me, id);
+    if (clipped && st) {
+      if (!clip.slot) return fail(CBX_ERR_INVALID, "%s: stepping replica %d without a slot list", me, id);
+      const int sl = clip.slot[id];
+      if (sl < 0 || sl >= cbx_sma_plan::kClipSlots)
+        return fail(CBX_ERR_INVALID, "%s: stepping replica %d: slot %d out of range [0, %d)", me, id, sl,
+                    cbx_sma_plan::kClipSlots);
+      if ((slots_taken >> sl) & 1ull)
+        return fail(CBX_ERR_INVALID, "%s: stepping replica %d: slot %d is another stepping replica's", me, id, sl);
+      slots_taken |= 1ull << sl;
+    }
     if (++participating > cbx::kMaxReplicas) continue;  // counted on, refused below
     const int k = a.nrep++;
+    slot_of[k] = clipped && st ? clip.slot[id] : -1;
     a.w[k] = reinterpret_cast<cbx::v4f *>(w[id]);
     a.s[k] = reinterpret_cast<cbx::v4f *>(s[id]);
     if (st) {
@@ -571,7 +605,25 @@ static int plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *
   HIP_TRY(hipSetDevice(d.hip_id));
   cbx::LaunchConfig cfg = p->task_barrier_cfg;
   cfg.num_cus = d.num_cus;
-  if (variables)
+  if (clipped && steps) {
+    // The norm passes in id order on the launch's stream, each over its slot's
+    // scratch (allocated on first use), as cbx_sma_plan_optimise_clipped runs
+    // them: the records are the sequence's bits.  No wait is queued.
+    cbx::ClipRecordPtrs records;
+    std::memset(&records, 0, sizeof(records));
+    cbx::ClipScratch *cs[cbx::kMaxReplicas] = {};
+    for (int k = 0; k < a.nrep; ++k)  // every scratch before the first launch: a failed allocation bumps no counter
+      if (slot_of[k] >= 0) TRY(clip_slot(p, me, 0, slot_of[k], &cs[k]));
+    for (int k = 0; k < a.nrep; ++k) {
+      if (!cs[k]) continue;
+      HIP_TRY(cbx::launch_gradient_norm(reinterpret_cast<const float *>(a.g[k]), p->n, *cs[k], clip.max_norm,
+                                        clip.skip_nonfinite == 1, p->clip_norm_policy,
+                                        static_cast<hipStream_t>(streams[0])));
+      records.p[k] = cs[k]->record();
+    }
+    HIP_TRY(cbx::launch_task_barrier_clipped(a, records, keep, cfg, static_cast<hipStream_t>(streams[0]),
+                                             p->next_timing()));
+  } else if (variables)
     HIP_TRY(cbx::launch_task_barrier_variables(a, d.var_tables, keep, cfg, static_cast<hipStream_t>(streams[0]),
                                                p->next_timing()));
   else
@@ -585,7 +637,7 @@ int cbx_sma_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float 
                                    const int *step, const float *learning_rate, float alpha, float momentum,
                                    float replica_momentum, float weight_decay, int first, unsigned flags) {
   return plan_step_and_optimise(p, streams, z, last, nreplicas, replica_device, w, s, g, rlast, locked, copy, step,
-                                learning_rate, alpha, momentum, replica_momentum, weight_decay, first, flags, false);
+                                learning_rate, alpha, momentum, replica_momentum, weight_decay, first, flags, SeamPlain);
 }
 
 int cbx_sma_plan_step_and_optimise_variables(cbx_sma_plan *p, void *const *streams, float *const *z,
@@ -595,7 +647,23 @@ int cbx_sma_plan_step_and_optimise_variables(cbx_sma_plan *p, void *const *strea
                                              const float *learning_rate, float alpha, float momentum,
                                              float replica_momentum, float weight_decay, int first, unsigned flags) {
   return plan_step_and_optimise(p, streams, z, last, nreplicas, replica_device, w, s, g, rlast, locked, copy, step,
-                                learning_rate, alpha, momentum, replica_momentum, weight_decay, first, flags, true);
+                                learning_rate, alpha, momentum, replica_momentum, weight_decay, first, flags,
+                                SeamVariables);
+}
+
+int cbx_sma_plan_step_and_optimise_clipped(cbx_sma_plan *p, void *const *streams, float *const *z, float *const *last,
+                                           int nreplicas, const int *replica_device, float *const *w, float *const *s,
+                                           float *const *g, float *const *rlast, const int *locked, const int *copy,
+                                           const int *step, const float *learning_rate, const int *slot,
+                                           float max_norm, int skip_nonfinite, float alpha, float momentum,
+                                           float replica_momentum, float weight_decay, int first, unsigned flags) {
+  SeamClip clip;
+  clip.slot = slot;
+  clip.max_norm = max_norm;
+  clip.skip_nonfinite = skip_nonfinite;
+  return plan_step_and_optimise(p, streams, z, last, nreplicas, replica_device, w, s, g, rlast, locked, copy, step,
+                                learning_rate, alpha, momentum, replica_momentum, weight_decay, first, flags,
+                                SeamClipped, clip);
 }
 
 // crossbowSynchronisationSynchronousSGD (synch/synchronoussgd.c:13-106) over

@@ -104,14 +104,29 @@ class SmaPlan:
         return self._step_and_optimise("cbx_sma_plan_step_and_optimise_variables", streams, z, last, replicas, alpha,
                                        momentum, replica_momentum, weight_decay, first, flags)
 
+    def step_and_optimise_clipped(self, streams, z, last, replicas, alpha: float, momentum: float,
+                                  replica_momentum: float, weight_decay: float, first: int = 0, flags: int = 0,
+                                  slots: Optional[Sequence[int]] = None, max_norm: float = 0.0,
+                                  skip_nonfinite: bool = False) -> int:
+        """``step_and_optimise`` with the clipped step of ``optimise_clipped``
+        (``cbx_sma_plan_step_and_optimise_clipped``): stepping replica id is
+        clipped to ``max_norm`` (0: none) through the record of ``slots[id]``,
+        whose norm pass the call runs on ``streams[0]`` first, and skipped when
+        ``skip_nonfinite`` and its gradient holds a NaN or an infinity.  Two
+        stepping replicas take two slots.  Otherwise the same arguments."""
+        return self._step_and_optimise("cbx_sma_plan_step_and_optimise_clipped", streams, z, last, replicas, alpha,
+                                       momentum, replica_momentum, weight_decay, first, flags,
+                                       (_ints(slots) if slots is not None else None, ctypes.c_float(max_norm),
+                                        1 if skip_nonfinite else 0))
+
     def _step_and_optimise(self, name, streams, z, last, replicas, alpha, momentum, replica_momentum, weight_decay,
-                           first, flags) -> int:
+                           first, flags, clip=()) -> int:
         rate = (ctypes.c_float * max(1, len(replicas)))(*[float(r[8]) for r in replicas])
         return _raise(self.lib, getattr(self.lib, name)(
             self._p, _ptrs(streams), _ptrs(z), _ptrs(last) if last is not None else None, len(replicas),
             _ints([r[0] for r in replicas]), _ptrs([r[1] for r in replicas]), _ptrs([r[2] for r in replicas]),
             _ptrs([r[3] for r in replicas]), _ptrs([r[4] for r in replicas]), _ints([r[5] for r in replicas]),
-            _ints([r[6] for r in replicas]), _ints([r[7] for r in replicas]), rate, ctypes.c_float(alpha),
+            _ints([r[6] for r in replicas]), _ints([r[7] for r in replicas]), rate, *clip, ctypes.c_float(alpha),
             ctypes.c_float(momentum), ctypes.c_float(replica_momentum), ctypes.c_float(weight_decay), first,
             ctypes.c_uint(flags)), name)
 

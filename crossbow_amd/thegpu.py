@@ -222,6 +222,16 @@ class TheGPU:
         return self._step_and_synchronise(self._L.cbx_step_and_synchronise_variables, first, clock, autotune, tasks,
                                           streams, flags)
 
+    def step_and_synchronise_clipped(self, first: int, clock: int, autotune: int, tasks: Sequence[int],
+                                     streams: Optional[Sequence[Optional[int]]] = None, flags: int = 0) -> int:
+        """``cbx_step_and_synchronise_clipped``: ``step_and_synchronise`` with
+        gradient clipping on (``setGradientClip``), which that call refuses:
+        each stepping replica's norm pass runs in front of the launch, and the
+        clipped (or skipped) step inside it.  Same arguments; with clipping
+        off it is that call."""
+        return self._step_and_synchronise(self._L.cbx_step_and_synchronise_clipped, first, clock, autotune, tasks,
+                                          streams, flags)
+
     def _step_and_synchronise(self, fn, first, clock, autotune, tasks, streams, flags) -> int:
         tasks = list(tasks)
         N = self.num_replicas()

@@ -277,6 +277,47 @@ int cbx_step_and_synchronise (cbx_context *ctx, int first, int clock, int autotu
  * cbx_step_and_synchronise: the same kernel, the same bits.                */
 int cbx_step_and_synchronise_variables (cbx_context *ctx, int first, int clock, int autotune,
                                         const int *tasks, void *const *streams, unsigned flags);
+/* cbx_step_and_synchronise with gradient clipping on (cbx_set_gradient_clip):
+ * every stepping replica's gradient is clipped to the global L2 norm, and a
+ * step whose gradient holds a NaN or an infinity is skipped, inside the one
+ * pass.  Same parameters, same checks and refusals in the same order and before
+ * the first side effect, except that clipping is honoured, not refused.
+ * cbx_set_variable_learning_rates on with a multiplier that is not 1 stays
+ * CBX_ERR_UNSUPPORTED: the clipped step with a rate per variable is not fused,
+ * take cbx_replica_optimise and cbx_synchronise.  A refused call launches no
+ * norm pass and bumps no counter of any record.
+ *
+ * The norm.  For every stepping replica, in id order, the norm pass and its
+ * reduce (the launches cbx_replica_optimise makes) go on streams[id] where
+ * given, else on the sync stream, in front of the fused launch, which is ordered
+ * behind them.  They leave S, K, scale, the flags and the running counts in the
+ * replica's cbx_clip_stats record on the device.
+ *
+ * The arithmetic.  Per element and per stepping replica i
+ *   g = scale_i * g           one fp32 multiply, before weight decay
+ * and then cbx_step_and_synchronise's sequence; scale_i and the flags are read
+ * from replica i's own record on the device.  A kept g_i is always written, as
+ * the clipped step writes it even without momentum and weight decay.  When the
+ * record carries the skip bit, w_i as the step sees it, g_i and last_i keep
+ * every bit (signalling NaNs and payloads included), s_i = w_i is a bit copy
+ * (written when outputs are kept), and the replica joins the barrier with
+ * s = w and w' = w.  Skipped wins over clipped.  The replicas of one call may
+ * differ: one unclipped at scale 1, one clipped, one skipped, one only joining.
+ *
+ * The contract.  With flags == 0, z, the base `last`, every replica's w, s, g
+ * and `last`, every replica's 48-byte cbx_clip_stats record (S, K, scale,
+ * flags and the three running counts) and every piece of host state are left
+ * bit for bit as after
+ *   cbx_replica_optimise (ctx, id, tasks[id], streams[id])  (clipping on)
+ *                                     for every id with tasks[id] >= 0, in id order,
+ *   cbx_synchronise (ctx, first, clock, autotune, 0).
+ * With CBX_STEP_DISCARD_TASK_OUTPUTS, s_i and g_i of the stepping replicas are
+ * not written; everything else is as above.
+ *
+ * With clipping off the call is cbx_step_and_synchronise: the same kernel, the
+ * same bits, and no launch for the norm.                                    */
+int cbx_step_and_synchronise_clipped (cbx_context *ctx, int first, int clock, int autotune,
+                                      const int *tasks, void *const *streams, unsigned flags);
 /* TheGPU.unlockAny() GPU.c:1142-1149 -> modelmanager.c:233-245           */
 int cbx_unlock_any (cbx_context *ctx);
 
@@ -985,6 +1026,38 @@ int cbx_sma_plan_step_and_optimise_variables (cbx_sma_plan *plan, void *const *s
                                               const float *learning_rate,
                                               float alpha, float momentum, float replica_momentum,
                                               float weight_decay, int first, unsigned flags);
+/* cbx_sma_plan_step_and_optimise with the clipped step of
+ * cbx_sma_plan_optimise_clipped: stepping replica id takes the record of
+ * slot[id] (the plan's device 0), whose norm pass and reduce the call launches
+ * on streams[0] in front of the fused launch, in id order; the slot's scratch
+ * is allocated on first use.  The arithmetic is cbx_step_and_synchronise_clipped's:
+ * g = scale * g before weight decay, a kept g[id] always written, and a replica
+ * whose record carries the skip bit keeps w (as the step sees it), g and rlast
+ * bit for bit, takes s = w and joins the barrier so.  max_norm == 0 and
+ * skip_nonfinite == 0 still run the reduction and count the step.  With
+ * flags == 0 every buffer and every slot's record is left bit for bit as after
+ *   cbx_sma_plan_optimise_clipped (plan, 0, slot[id], streams[0], w[id], g[id],
+ *       rlast[id], s[id], learning_rate[id], replica_momentum, weight_decay,
+ *       max_norm, skip_nonfinite, 0)     for every id with step[id] != 0, in id order,
+ *   cbx_sma_plan_step (plan, streams, z, last, nreplicas, replica_device, w, s,
+ *       locked, copy, alpha, momentum, first);
+ * with CBX_STEP_DISCARD_TASK_OUTPUTS, s[id] and g[id] of the stepping replicas
+ * are not written.  Checks and refusals are cbx_sma_plan_step_and_optimise's,
+ * all before the first launch (a refused call bumps no counter), and
+ * CBX_ERR_INVALID besides: max_norm negative, NaN or infinite; skip_nonfinite
+ * neither 0 nor 1; a NULL `slot` with a stepping replica; a stepping replica's
+ * slot outside [0, 64); two stepping replicas sharing a slot.  slot[id] of a
+ * replica that does not step is not read.  The plan queues no wait of its own. */
+int cbx_sma_plan_step_and_optimise_clipped (cbx_sma_plan *plan, void *const *streams,
+                                            float *const *z, float *const *last,
+                                            int nreplicas, const int *replica_device,
+                                            float *const *w, float *const *s, float *const *g,
+                                            float *const *rlast,
+                                            const int *locked, const int *copy, const int *step,
+                                            const float *learning_rate,
+                                            const int *slot, float max_norm, int skip_nonfinite,
+                                            float alpha, float momentum, float replica_momentum,
+                                            float weight_decay, int first, unsigned flags);
 /* The statistics reduction of cbx_model_stats over caller-owned buffers of
  * exactly the plan's `elements` floats on the plan's device k (where a
  * Crossbow build would checksum, databuffer.c:141-162): `ref` against

@@ -1,0 +1,106 @@
+"""``cbx_step_and_synchronise_clipped`` and
+``cbx_sma_plan_step_and_optimise_clipped`` without a GPU: both are declared in
+the header, bound in ``crossbow_amd._abi`` and exported by the built library;
+the context call has the parameters of the call it extends, the seam call those
+plus ``slot``, ``max_norm`` and ``skip_nonfinite``; ``thegpu.py`` and
+``seam.py`` expose them; a NULL context or plan is an error, not a crash; and
+their kernels live in a shared object of their own that every build takes."""
+from __future__ import annotations
+
+import ctypes
+import inspect
+import os
+import re
+import shutil
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CONTEXT, SEAM = "cbx_step_and_synchronise_clipped", "cbx_sma_plan_step_and_optimise_clipped"
+SOURCE = "crossbow_amd/csrc/task_barrier_clipped_kernels.hip"
+
+
+def _header():
+    with open(os.path.join(ROOT, "include", "crossbow_sma.h")) as f:
+        return f.read()
+
+
+def _declared(name):
+    m = re.search(r"int %s \(([^;]*)\);" % name, _header())
+    assert m, name
+    return [" ".join(a.split()) for a in m.group(1).split(",") if a.strip()]
+
+
+def test_the_symbols_are_declared_bound_and_exported():
+    from crossbow_amd import _abi, _lib
+    lib = _lib.load()
+    header = _header()
+    for name in (CONTEXT, SEAM):
+        assert f"int {name} (" in header, name
+        assert name in _abi.SIGNATURES, name
+        assert getattr(lib, name).argtypes == _abi.SIGNATURES[name][1], name
+        assert getattr(lib, name).restype == ctypes.c_int
+    assert "#define CBX_ABI_VERSION 1" in header
+
+
+def test_the_context_call_has_the_plain_calls_parameters():
+    from crossbow_amd import _abi
+    assert _declared(CONTEXT) == _declared("cbx_step_and_synchronise")
+    assert _abi.SIGNATURES[CONTEXT] == _abi.SIGNATURES["cbx_step_and_synchronise"]
+
+
+def test_the_seam_call_adds_the_slots_and_the_two_clip_arguments():
+    from crossbow_amd import _abi
+    plain, clipped = _declared("cbx_sma_plan_step_and_optimise"), _declared(SEAM)
+    at = plain.index("const float *learning_rate") + 1
+    assert clipped == plain[:at] + ["const int *slot", "float max_norm", "int skip_nonfinite"] + plain[at:]
+    p, c = _abi.SIGNATURES["cbx_sma_plan_step_and_optimise"][1], _abi.SIGNATURES[SEAM][1]
+    assert c == p[:at] + [ctypes.POINTER(ctypes.c_int), ctypes.c_float, ctypes.c_int] + p[at:]
+
+
+def test_the_python_wrappers_expose_the_calls():
+    from crossbow_amd.seam import SmaPlan
+    from crossbow_amd.thegpu import TheGPU
+    assert list(inspect.signature(TheGPU.step_and_synchronise_clipped).parameters) == \
+        list(inspect.signature(TheGPU.step_and_synchronise).parameters)
+    assert list(inspect.signature(SmaPlan.step_and_optimise_clipped).parameters) == \
+        list(inspect.signature(SmaPlan.step_and_optimise).parameters) + ["slots", "max_norm", "skip_nonfinite"]
+
+
+def test_a_null_context_or_plan_is_an_error_not_a_crash():
+    from crossbow_amd import _lib
+    lib = _lib.load()
+    tasks = (ctypes.c_int * 1)(0)
+    assert lib.cbx_step_and_synchronise_clipped(None, 0, 1, 0, tasks, None, 0) == _lib.CBX_ERR_INVALID
+    assert b"null" in lib.cbx_last_error()
+    rc = lib.cbx_sma_plan_step_and_optimise_clipped(None, None, None, None, 0, None, None, None, None, None, None,
+                                                    None, None, None, None, 1.0, 0, 0.1, 0.9, 0.9, 0.0, 0, 0)
+    assert rc == _lib.CBX_ERR_INVALID
+    assert b"null" in lib.cbx_last_error()
+
+
+def test_the_kernels_are_a_shared_object_of_their_own_in_every_build():
+    from crossbow_amd import build
+    assert build.CLIPPED_SOURCES == ("task_barrier_clipped_kernels.hip",)
+    assert "task_barrier_clipped_kernels.hip" not in build.SOURCES + build.VARIABLES_SOURCES
+    assert os.path.basename(build.CLIPPED_LIB) == "libcrossbow_sma_clipped.so"
+    assert os.path.exists(build.CLIPPED_LIB), "python __graft_entry__.py builds it"
+    # the library names it as a dependency found beside itself
+    with open(build.LIB, "rb") as f:
+        blob = f.read()
+    assert b"libcrossbow_sma_clipped.so" in blob and b"$ORIGIN" in blob
+    # the one staleness check covers it
+    assert os.path.join(build.CSRC, "task_barrier_clipped_kernels.hip") in build._deps()
+    for script in ("scripts/build_sanitized.sh", "scripts/build_fake_rccl.sh", "__graft_entry__.py"):
+        with open(os.path.join(ROOT, script)) as f:
+            assert SOURCE in f.read(), script
+
+
+def test_the_device_code_of_the_main_library_holds_no_new_kernel():
+    from crossbow_amd import build
+    tool = shutil.which("nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    main, own, variables = (subprocess.run([tool, "-C", "--defined-only", lib], check=True, capture_output=True,
+                                           text=True).stdout
+                            for lib in (build.LIB, build.CLIPPED_LIB, build.VARIABLES_LIB))
+    assert "task_barrier_clipped_kernel" not in main and "task_barrier_clipped_kernel" not in variables
+    assert "task_barrier_clipped_kernel" in own and "launch_task_barrier_clipped" in own
+    assert len(build.code_object_digest(build.CLIPPED_LIB)) == 64
