@@ -48,7 +48,9 @@ SOURCES = ("context.hip", "sync_steps.hip", "sma_kernels.hip", "averaging_kernel
 VARIABLES_SOURCES = ("task_barrier_variables_kernels.hip",)
 CLIPPED_SOURCES = ("task_barrier_clipped_kernels.hip",)
 HEADERS = ("context_internal.h", "sma_internal.h", "stream_helpers.h", "stats_internal.h", "stats_plan.h",
-           "optimise_plan.h", "clip_internal.h", "bucket_pipeline.h")
+           "optimise_plan.h", "clip_internal.h", "bucket_pipeline.h",
+           # the fused task-step barrier's three kernel files are one text
+           "task_barrier_step.h", "task_barrier_body.inc", "task_barrier_launch.h")
 
 
 def _sources(names=SOURCES):

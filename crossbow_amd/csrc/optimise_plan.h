@@ -1,7 +1,8 @@
 // optimise_plan.h -- the chunk table of the per-variable replica step
 // (variable_rate_kernels.hip, cbx_set_variable_learning_rates,
-// cbx_replica_optimise_variables).  Plain C++, no HIP: the builder is tested
-// on the CPU (tests/native/optimise_plan_test.cpp).
+// cbx_replica_optimise_variables), and the kernels' lookup in it (variable_of).
+// Plain C++ that needs no HIP: the builder and the lookup are tested on the
+// CPU (tests/native/optimise_plan_test.cpp).
 //
 // A model buffer is a run of variables whose offsets are a running sum
 // (ModelDef::offset, model.c:127-157), not multiples of 16 bytes.  The kernel
@@ -35,6 +36,25 @@ struct OptimisePlan {
 
 inline uint32_t opt_chunk_var(uint32_t entry) { return entry >> 1; }
 inline bool opt_chunk_mixed(uint32_t entry) { return (entry & 1u) != 0; }
+
+#ifdef __HIPCC__
+#define CBX_OPT_INLINE __host__ __device__ __forceinline__
+#else
+#define CBX_OPT_INLINE inline
+#endif
+// The kernels' lookup in a mixed chunk: the variable of float f, at or after v0
+// (the variable of the chunk's first float), i.e. the last v with
+// bounds[v] <= f.  bounds[nvars] = elements > f.
+CBX_OPT_INLINE uint32_t variable_of(const uint32_t *__restrict__ bounds, uint32_t nvars, uint32_t v0, uint32_t f) {
+  uint32_t lo = v0, hi = nvars;
+  while (hi - lo > 1u) {
+    const uint32_t m = (lo + hi) >> 1;
+    if (bounds[m] <= f) lo = m;
+    else hi = m;
+  }
+  return lo;
+}
+#undef CBX_OPT_INLINE
 
 // var_elements[0 .. nvars): floats per variable, in offset order; they must
 // sum to `elements`.  False on no variables, negative counts, a wrong sum, or

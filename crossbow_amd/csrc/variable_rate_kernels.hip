@@ -43,19 +43,6 @@
 namespace cbx {
 namespace {
 
-// The variable of float f, at or after v0 (the variable of the chunk's first
-// float): the last v with bounds[v] <= f.  bounds[nvars] = elements > f.
-__device__ __forceinline__ uint32_t variable_of(const uint32_t *__restrict__ bounds, uint32_t nvars, uint32_t v0,
-                                                uint32_t f) {
-  uint32_t lo = v0, hi = nvars;
-  while (hi - lo > 1u) {
-    const uint32_t m = (lo + hi) >> 1;
-    if (bounds[m] <= f) lo = m;
-    else hi = m;
-  }
-  return lo;
-}
-
 // CLIP: as sma_optimise_kernel's (sma_kernels.hip): g = scale * g before weight
 // decay on all three paths, s = w alone when the record carries the skip bit.
 template <bool MOM, bool WD, int P, int U, bool CLIP>

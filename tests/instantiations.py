@@ -234,18 +234,18 @@ def _task_barrier(case: Case, num_cus: int) -> str:
     stepping = case.steps != "none"
     mom = case.rep_mom and stepping  # context.hip:775, sma_seam.hip:561: the first stepping replica's, else 0
     wd = case.wd and stepping        # context.hip:776, sma_seam.hip:562
-    # tb_form, task_barrier_kernels.hip:306-310
+    # the ladders are task_barrier_launch.h's, named here by function (the three barrier objects share them): tb_form
     if case.nrep > 0 and case.steps == "all" and case.base_mom == mom:
-        R, mixed, bmom = _ladder(case.nrep, range(1, K_CHUNK + 1)), False, mom  # tb_all, :285-295
+        R, mixed, bmom = _ladder(case.nrep, range(1, K_CHUNK + 1)), False, mom  # tb_form's switch
     else:
-        R, mixed, bmom = -1, True, case.base_mom  # tb_mixed, :301-303
-    u = small_launch_shape(block, bpc, unroll, waves, n4, num_cus)  # tb_u, :231
+        R, mixed, bmom = -1, True, case.base_mom  # tb_form's last return
+    u = small_launch_shape(block, bpc, unroll, waves, n4, num_cus)  # tb_u
     if tail and P != 1:
-        raise Refused("a tail needs policy 1")  # :253-254
+        raise Refused("a tail needs policy 1")  # task_barrier_compiled
     if u not in (1, 2):
-        raise Refused(f"unroll {u}")  # :259-277
+        raise Refused(f"unroll {u}")  # tb_u
     return (f"task_barrier_kernel<{R}, {_b(mixed)}, {_b(mom)}, {_b(bmom)}, {_b(wd)}, {_b(case.keep)}, {P}, "
-            f"{_b(tail)}, {u}>")  # tb_conf / launch_task_barrier, :313-329
+            f"{_b(tail)}, {u}>")  # tb_conf / task_barrier_launch
 
 
 def _averaging(case: Case, num_cus: int) -> List[str]:

@@ -39,11 +39,11 @@ def expected_kernel(case: Case, num_cus: int) -> str:
     block, bpc, unroll, waves = I._main_cfg(case)
     n4, tail, P = I.bulk_float4s(case, num_cus), I.has_tail(case, num_cus), I._policy(case)
     mom, wd = case.rep_mom, case.wd  # the first stepping replica's
-    if case.steps == "all" and case.base_mom == mom:  # tbc_form
-        R, mixed, bmom = I._ladder(case.nrep, range(1, I.K_CHUNK + 1)), False, mom  # tbc_all
+    if case.steps == "all" and case.base_mom == mom:  # tb_form (task_barrier_launch.h)
+        R, mixed, bmom = I._ladder(case.nrep, range(1, I.K_CHUNK + 1)), False, mom  # tb_form's switch
     else:
         R, mixed, bmom = -1, True, case.base_mom
-    u = I.small_launch_shape(block, bpc, unroll, waves, n4, num_cus)  # tbc_u
+    u = I.small_launch_shape(block, bpc, unroll, waves, n4, num_cus)  # tb_u
     if tail:
         if P != 1 or u != 1:
             raise I.Refused("a tail has policy 1 and unroll 1")

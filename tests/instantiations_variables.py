@@ -9,7 +9,7 @@ tests/instantiations.py:
 
 ``CASES``       one call each, with everything the dispatch looks at: the cases
                 of the plain fused barrier (tests/instantiations.py), whose
-                ladders the new launcher repeats, over a model of several
+                ladders the launcher shares (task_barrier_launch.h), over a model of several
                 variables (``variables_for``).
                 tests/test_gpu_instantiations_variables.py runs every one
                 against the oracle, bit for bit.
@@ -45,7 +45,8 @@ def variables_for(n: int) -> Tuple[Tuple[int, ...], Tuple[float, ...]]:
 
 
 def expected_kernel(case: Case, num_cus: int) -> str:
-    """launch_task_barrier_variables, task_barrier_variables_kernels.hip:371-387."""
+    """launch_task_barrier_variables: the ladders of task_barrier_launch.h, named by function, with what
+    VariablesLauncher (task_barrier_variables_kernels.hip) says of a side object."""
     if case.family != "task_barrier":
         raise ValueError(case.family)
     block, bpc, unroll, waves = I._main_cfg(case)
@@ -55,20 +56,20 @@ def expected_kernel(case: Case, num_cus: int) -> str:
     stepping = case.steps != "none"
     mom = case.rep_mom and stepping  # context.hip:796, sma_seam.hip:565: the first stepping replica's, else 0
     wd = case.wd and stepping
-    # tbv_form, :352-358
+    # tb_form
     if case.nrep > 0 and case.steps == "all" and case.base_mom == mom:
-        R, mixed, bmom = I._ladder(case.nrep, range(1, I.K_CHUNK + 1)), False, mom  # tbv_all, :337-349
+        R, mixed, bmom = I._ladder(case.nrep, range(1, I.K_CHUNK + 1)), False, mom  # tb_form's switch
     else:
         R, mixed, bmom = -1, True, case.base_mom
-    u = I.small_launch_shape(block, bpc, unroll, waves, n4, num_cus)  # tbv_u, :286
+    u = I.small_launch_shape(block, bpc, unroll, waves, n4, num_cus)  # tb_u
     if tail:
         if P != 1 or u != 1:
-            raise I.Refused("a tail has policy 1 and unroll 1")  # :299-303
+            raise I.Refused("a tail has policy 1 and unroll 1")  # task_barrier_compiled, kSideObject
         U = 1
     else:
-        seam_only = mixed and not mom and bmom and wd  # :316
+        seam_only = mixed and not mom and bmom and wd  # VariablesLauncher::seam_only
         if u not in (1, 2) or (seam_only and (P != 1 or u != 1)):
-            raise I.Refused(f"policy {P}, unroll {u}")  # :317-332
+            raise I.Refused(f"policy {P}, unroll {u}")  # tb_u, task_barrier_compiled
         U = u
     b = I._b
     return f"{KERNEL}<{R}, {b(mixed)}, {b(mom)}, {b(bmom)}, {b(wd)}, {b(case.keep)}, {P}, {b(tail)}, {U}>"

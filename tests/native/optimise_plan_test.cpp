@@ -20,17 +20,6 @@
     }                                                                      \
   } while (0)
 
-// variable_of of variable_rate_kernels.hip, word for word.
-static uint32_t variable_of(const uint32_t *bounds, uint32_t nvars, uint32_t v0, uint32_t f) {
-  uint32_t lo = v0, hi = nvars;
-  while (hi - lo > 1u) {
-    const uint32_t m = (lo + hi) >> 1;
-    if (bounds[m] <= f) lo = m;
-    else hi = m;
-  }
-  return lo;
-}
-
 static size_t check_case(const std::vector<long long> &vars) {
   long long n = 0;
   for (long long e : vars) n += e;
@@ -61,7 +50,7 @@ static size_t check_case(const std::vector<long long> &vars) {
     CHECK(cbx::opt_chunk_var(entry) == owner[(size_t)lo]);
     for (uint64_t f = lo; f < hi && f < (uint64_t)n; ++f) {
       const uint32_t v = cbx::opt_chunk_mixed(entry)
-                             ? variable_of(plan.bounds.data(), V, cbx::opt_chunk_var(entry), (uint32_t)f)
+                             ? cbx::variable_of(plan.bounds.data(), V, cbx::opt_chunk_var(entry), (uint32_t)f)
                              : cbx::opt_chunk_var(entry);
       CHECK(v == owner[(size_t)f]);
     }

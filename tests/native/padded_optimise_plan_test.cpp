@@ -19,17 +19,6 @@
     }                                                                      \
   } while (0)
 
-// variable_of of task_barrier_variables_kernels.hip, word for word.
-static uint32_t variable_of(const uint32_t *bounds, uint32_t nvars, uint32_t v0, uint32_t f) {
-  uint32_t lo = v0, hi = nvars;
-  while (hi - lo > 1u) {
-    const uint32_t m = (lo + hi) >> 1;
-    if (bounds[m] <= f) lo = m;
-    else hi = m;
-  }
-  return lo;
-}
-
 constexpr long long kPadFloats = 4096;  // kPadFloat4 float4s
 
 static size_t check_case(const std::vector<long long> &vars) {
@@ -53,7 +42,7 @@ static size_t check_case(const std::vector<long long> &vars) {
     CHECK(cbx::opt_chunk_var(entry) <= V);
     for (uint64_t f = (uint64_t)c * cbx::kOptChunk; f < (uint64_t)(c + 1) * cbx::kOptChunk; ++f) {
       const uint32_t v = cbx::opt_chunk_mixed(entry)
-                             ? variable_of(plan.bounds.data(), V + 1, cbx::opt_chunk_var(entry), (uint32_t)f)
+                             ? cbx::variable_of(plan.bounds.data(), V + 1, cbx::opt_chunk_var(entry), (uint32_t)f)
                              : cbx::opt_chunk_var(entry);
       if (f < (uint64_t)n) {
         CHECK(v == owner[(size_t)f]);

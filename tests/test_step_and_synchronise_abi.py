@@ -74,6 +74,9 @@ def test_null_context_is_an_error_not_a_crash():
 def test_the_kernel_file_is_part_of_every_build_of_the_library():
     from crossbow_amd import build
     assert "task_barrier_kernels.hip" in build.SOURCES
+    # the text it shares with the per-variable and the clipped kernel makes the library stale too
+    for shared in ("task_barrier_step.h", "task_barrier_body.inc", "task_barrier_launch.h"):
+        assert os.path.join(build.CSRC, shared) in build._deps(), shared
     for script in ("build_sanitized.sh", "build_fake_rccl.sh"):
         with open(os.path.join(ROOT, "scripts", script)) as f:
             assert "crossbow_amd/csrc/task_barrier_kernels.hip" in f.read(), script

@@ -90,6 +90,9 @@ def test_the_kernels_are_a_shared_object_of_their_own_in_every_build():
     assert b"libcrossbow_sma_clipped.so" in blob and b"$ORIGIN" in blob
     # the one staleness check covers it
     assert os.path.join(build.CSRC, "task_barrier_clipped_kernels.hip") in build._deps()
+    # and the text the three barrier kernels share
+    for shared in ("task_barrier_step.h", "task_barrier_body.inc", "task_barrier_launch.h", "clip_internal.h"):
+        assert os.path.join(build.CSRC, shared) in build._deps(), shared
     for script in ("scripts/build_sanitized.sh", "scripts/build_fake_rccl.sh", "__graft_entry__.py"):
         with open(os.path.join(ROOT, script)) as f:
             assert SOURCE in f.read(), script

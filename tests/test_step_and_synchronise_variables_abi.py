@@ -104,6 +104,9 @@ def test_the_kernels_are_a_shared_object_of_their_own_in_every_build():
     # the staleness check covers both libraries
     deps = build._deps()
     assert os.path.join(build.CSRC, "task_barrier_variables_kernels.hip") in deps
+    # and the text the three barrier kernels share
+    for shared in ("task_barrier_step.h", "task_barrier_body.inc", "task_barrier_launch.h", "optimise_plan.h"):
+        assert os.path.join(build.CSRC, shared) in deps, shared
     for script in ("build_sanitized.sh", "build_fake_rccl.sh"):
         with open(os.path.join(ROOT, "scripts", script)) as f:
             assert "crossbow_amd/csrc/task_barrier_variables_kernels.hip" in f.read(), script
