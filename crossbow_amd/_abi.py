@@ -115,6 +115,7 @@ SIGNATURES = {
     "cbx_step_and_synchronise": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
     "cbx_step_and_synchronise_variables": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
     "cbx_step_and_synchronise_clipped": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
+    "cbx_step_and_synchronise_clipped_variables": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
     "cbx_unlock_any": (_I, [_P]),
     "cbx_checkpoint_model": (_I, [_P, _CP]),
     "cbx_override_model_data": (_I, [_P, _CP]),
@@ -200,6 +201,9 @@ SIGNATURES = {
                                                       _FP, _F, _F, _F, _F, _I, _c.c_uint]),
     "cbx_sma_plan_step_and_optimise_clipped": (_I, [_P, _PP, _PP, _PP, _I, _IP, _PP, _PP, _PP, _PP, _IP, _IP, _IP,
                                                     _FP, _IP, _F, _I, _F, _F, _F, _F, _I, _c.c_uint]),
+    "cbx_sma_plan_step_and_optimise_clipped_variables": (_I, [_P, _PP, _PP, _PP, _I, _IP, _PP, _PP, _PP, _PP, _IP,
+                                                              _IP, _IP, _FP, _IP, _F, _I, _F, _F, _F, _F, _I,
+                                                              _c.c_uint]),
     "cbx_sma_plan_buffer_stats": (_I, [_P, _I, _P, _P, _PP, _I, _LLP, _I, _BS, _BS, _BS, _BS]),
     "cbx_sma_optimise_buffers": (_I, [_P, _P, _P, _P, _P, _c.c_longlong, _F, _F, _F]),
     "cbx_sma_plan_set_variables": (_I, [_P, _LLP, _FP, _I]),

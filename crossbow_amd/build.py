@@ -12,6 +12,8 @@
 * ``crossbow_amd/libcrossbow_sma_clipped.so`` -- the fused task-step barrier
   with gradient clipping (csrc/task_barrier_clipped_kernels.hip): likewise a
   shared object of its own, built first and linked by the library.
+* ``crossbow_amd/libcrossbow_sma_clipped_variables.so`` -- the fused task-step
+  barrier with both (csrc/task_barrier_clipped_variables_kernels.hip): likewise.
 * ``crossbow_amd/libGPU.so``           -- the JNI shim exporting Crossbow's
   ``TheGPU`` model-path natives; built only where ``jni.h`` exists (there is
   no JDK in this image).
@@ -32,6 +34,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libcrossbow_sma.so")
 VARIABLES_LIB = os.path.join(PKG, "libcrossbow_sma_variables.so")
 CLIPPED_LIB = os.path.join(PKG, "libcrossbow_sma_clipped.so")
+CLIPPED_VARIABLES_LIB = os.path.join(PKG, "libcrossbow_sma_clipped_variables.so")
 JNI_LIB = os.path.join(PKG, "libGPU.so")
 ARCH = "gfx950"
 
@@ -47,9 +50,10 @@ SOURCES = ("context.hip", "sync_steps.hip", "sma_kernels.hip", "averaging_kernel
            "stats_kernels.hip", "variable_rate_kernels.hip", "clip_kernels.hip", "task_barrier_kernels.hip")
 VARIABLES_SOURCES = ("task_barrier_variables_kernels.hip",)
 CLIPPED_SOURCES = ("task_barrier_clipped_kernels.hip",)
+CLIPPED_VARIABLES_SOURCES = ("task_barrier_clipped_variables_kernels.hip",)
 HEADERS = ("context_internal.h", "sma_internal.h", "stream_helpers.h", "stats_internal.h", "stats_plan.h",
            "optimise_plan.h", "clip_internal.h", "bucket_pipeline.h",
-           # the fused task-step barrier's three kernel files are one text
+           # the fused task-step barrier's four kernel files are one text
            "task_barrier_step.h", "task_barrier_body.inc", "task_barrier_launch.h")
 
 
@@ -59,6 +63,7 @@ def _sources(names=SOURCES):
 
 def _deps():
     return (_sources() + _sources(VARIABLES_SOURCES) + _sources(CLIPPED_SOURCES) +
+            _sources(CLIPPED_VARIABLES_SOURCES) +
             [os.path.join(CSRC, f) for f in HEADERS] + [os.path.join(ROOT, "include", "crossbow_sma.h"),
                                                         os.path.abspath(__file__)])
 
@@ -70,25 +75,39 @@ def _stale(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _jobs() -> int:
+    """Compilations at a time: $MAX_JOBS, else the CPUs this process may use, 16 at the most."""
+    try:
+        n = int(os.environ.get("MAX_JOBS", ""))
+    except ValueError:
+        n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    return max(1, min(n, 16))
+
+
+def _compile_one(src, objdir, verbose):
+    stem = os.path.splitext(os.path.basename(src))[0]
+    obj = os.path.join(objdir, stem + ".o")
+    cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall",
+           # A fixed compilation-unit id per source instead of one hashed from
+           # its path: the device code (and code_object_digest) is then the
+           # same wherever the tree is built.
+           f"-cuid=crossbow_{stem}",
+           # fp32 results must equal the reference's cuBLAS op order bit for bit: every
+           # fma is written explicitly, nothing may be contracted behind our back.
+           "-ffp-contract=off",
+           "-I", os.path.join(ROOT, "include"), "-c", "-o", obj, src]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    return obj
+
+
 def _compile(sources, objdir, verbose):
-    objs = []
-    for src in sources:
-        stem = os.path.splitext(os.path.basename(src))[0]
-        obj = os.path.join(objdir, stem + ".o")
-        cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall",
-               # A fixed compilation-unit id per source instead of one hashed from
-               # its path: the device code (and code_object_digest) is then the
-               # same wherever the tree is built.
-               f"-cuid=crossbow_{stem}",
-               # fp32 results must equal the reference's cuBLAS op order bit for bit: every
-               # fma is written explicitly, nothing may be contracted behind our back.
-               "-ffp-contract=off",
-               "-I", os.path.join(ROOT, "include"), "-c", "-o", obj, src]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.run(cmd, check=True)
-        objs.append(obj)
-    return objs
+    """One object per source, in the sources' order; the compilations run side
+    by side (each is one hipcc process), the first failure is raised."""
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=_jobs()) as pool:
+        return list(pool.map(lambda src: _compile_one(src, objdir, verbose), sources))
 
 
 def _link(target, objs, libs, verbose):
@@ -101,16 +120,24 @@ def _link(target, objs, libs, verbose):
 
 
 def build_lib(force: bool = False, verbose: bool = False) -> str:
-    # one staleness check for all three libraries: they share the headers
-    if not force and not any(_stale(t, _deps()) for t in (LIB, VARIABLES_LIB, CLIPPED_LIB)):
+    # one staleness check for all four libraries: they share the headers
+    if not force and not any(_stale(t, _deps()) for t in (LIB, VARIABLES_LIB, CLIPPED_LIB, CLIPPED_VARIABLES_LIB)):
         return LIB
     objdir = os.path.join(PKG, "build")
     os.makedirs(objdir, exist_ok=True)
-    # the objects of the per-variable and the clipped fused barrier first: the library links against them
-    _link(VARIABLES_LIB, _compile(_sources(VARIABLES_SOURCES), objdir, verbose), [], verbose)
-    _link(CLIPPED_LIB, _compile(_sources(CLIPPED_SOURCES), objdir, verbose), [], verbose)
-    _link(LIB, _compile(_sources(), objdir, verbose),
-          ["-L", PKG, "-lcrossbow_sma_variables", "-lcrossbow_sma_clipped", "-Wl,-rpath,$ORIGIN", "-lrccl", "-lrocprofiler-sdk-roctx", "-lpthread"],
+    # every source of the four objects is compiled in one pool, the slowest (the barrier kernels) first
+    groups = (VARIABLES_SOURCES, CLIPPED_SOURCES, CLIPPED_VARIABLES_SOURCES, tuple(reversed(SOURCES)))
+    objs = _compile([src for names in groups for src in _sources(names)], objdir, verbose)
+    side = (len(VARIABLES_SOURCES), len(CLIPPED_SOURCES), len(CLIPPED_VARIABLES_SOURCES))
+    at = [sum(side[:k]) for k in range(4)]
+    # the objects of the per-variable, the clipped and the clipped per-variable fused barrier first: the library
+    # links against them
+    _link(VARIABLES_LIB, objs[at[0]:at[1]], [], verbose)
+    _link(CLIPPED_LIB, objs[at[1]:at[2]], [], verbose)
+    _link(CLIPPED_VARIABLES_LIB, objs[at[2]:at[3]], [], verbose)
+    _link(LIB, list(reversed(objs[at[3]:])),
+          ["-L", PKG, "-lcrossbow_sma_variables", "-lcrossbow_sma_clipped", "-lcrossbow_sma_clipped_variables",
+           "-Wl,-rpath,$ORIGIN", "-lrccl", "-lrocprofiler-sdk-roctx", "-lpthread"],
           verbose)
     return LIB
 

@@ -92,5 +92,14 @@ struct ClipRecordPtrs {
 // hipErrorInvalidValue, before the launch.
 hipError_t launch_task_barrier_clipped(const TaskBarrierArgs &a, const ClipRecordPtrs &rec, bool keep_task_outputs,
                                        const LaunchConfig &cfg, hipStream_t stream, Timing t = {});
+// launch_task_barrier_clipped with a learning rate per variable
+// (task_barrier_clipped_variables_kernels.hip, a shared object of its own:
+// libcrossbow_sma_clipped_variables.so): stepping replica k clips as above and
+// steps with a.rate[k] * t.mult[v], launch_sma_optimise_variables_clipped's
+// bits per replica.  The tables as for launch_task_barrier_variables, the
+// records and the compiled forms as for launch_task_barrier_clipped.
+hipError_t launch_task_barrier_clipped_variables(const TaskBarrierArgs &a, const VarTables &t,
+                                                 const ClipRecordPtrs &rec, bool keep_task_outputs,
+                                                 const LaunchConfig &cfg, hipStream_t stream, Timing tm = {});
 
 }  // namespace cbx

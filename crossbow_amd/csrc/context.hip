@@ -697,15 +697,22 @@ int cbx_synchronise_staged(cbx_context *c, int first, int clock, int autotune, i
 // call refuses them.  FusedClipped: cbx_step_and_synchronise_clipped, which
 // runs every stepping replica's norm pass in front of the launch and the
 // clipped step inside it (task_barrier_clipped_kernels.hip) where the plain
-// call refuses clipping.  Everything else is one code path.
-enum FusedMode { FusedPlain, FusedVariables, FusedClipped };
+// call refuses clipping.  FusedClippedVariables:
+// cbx_step_and_synchronise_clipped_variables, which refuses neither: with both
+// on and a stepping replica it runs the norm passes as the clipped call places
+// them and the kernel that is both (task_barrier_clipped_variables_kernels.hip);
+// with one of them off, or nobody stepping, it launches what the call for the
+// other one launches.  Everything else is one code path.
+enum FusedMode { FusedPlain, FusedVariables, FusedClipped, FusedClippedVariables };
 
 static int step_and_synchronise(cbx_context *c, int first, int clock, int autotune, const int *tasks,
                                 void *const *streams, unsigned flags, FusedMode mode) {
-  const bool variables = mode == FusedVariables;
-  const char *me = mode == FusedClipped ? "cbx_step_and_synchronise_clipped"
-                   : variables          ? "cbx_step_and_synchronise_variables"
-                                        : "cbx_step_and_synchronise";
+  const bool variables = mode == FusedVariables || mode == FusedClippedVariables;
+  const bool clips = mode == FusedClipped || mode == FusedClippedVariables;
+  const char *me = mode == FusedClippedVariables ? "cbx_step_and_synchronise_clipped_variables"
+                   : mode == FusedClipped        ? "cbx_step_and_synchronise_clipped"
+                   : variables                   ? "cbx_step_and_synchronise_variables"
+                                                 : "cbx_step_and_synchronise";
   TraceRange trace(me);
   TRY(check_manager_q(c));
   if (first < 0 || first > c->size) return fail(CBX_ERR_INVALID, "first replica %d out of range", first);
@@ -732,14 +739,15 @@ static int step_and_synchronise(cbx_context *c, int first, int clock, int autotu
   if (type != CBX_UPDATE_SMA && type != CBX_UPDATE_SYNCHRONOUSEAMSGD)
     return fail(CBX_ERR_UNSUPPORTED, "%s: update model %d; only SMA (7) and SYNCHRONOUSEAMSGD (3) are fused", me, type);
   const bool clip = c->clip_on();
-  if (clip && mode != FusedClipped)
-    return fail(CBX_ERR_UNSUPPORTED, "%s: gradient clipping is on; the clipped step needs its norm pass first, use "
-                "cbx_replica_optimise and cbx_synchronise", me);
   const bool per_variable = c->variable_rates && c->model.conf.irregular > 0;
+  if (clip && !clips)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: gradient clipping is on; the clipped step needs its norm pass first, use %s, "
+                "or cbx_replica_optimise and cbx_synchronise", me,
+                per_variable ? "cbx_step_and_synchronise_clipped_variables" : "cbx_step_and_synchronise_clipped");
   if (per_variable && !variables)
-    return fail(CBX_ERR_UNSUPPORTED, "%s: variable learning rates are on with %d irregular variables; %suse "
+    return fail(CBX_ERR_UNSUPPORTED, "%s: variable learning rates are on with %d irregular variables; use %s, or "
                 "cbx_replica_optimise and cbx_synchronise", me, c->model.conf.irregular,
-                mode == FusedClipped ? "the clipped step with a rate per variable is not fused, " : "");
+                clip ? "cbx_step_and_synchronise_clipped_variables" : "cbx_step_and_synchronise_variables");
   if (per_variable && !c->var_refusal.empty())
     return fail(CBX_ERR_UNSUPPORTED, "%s with variable learning rates: %s", me, c->var_refusal.c_str());
   Device &d = c->devs[0];
@@ -849,8 +857,10 @@ static int step_and_synchronise(cbx_context *c, int first, int clock, int autotu
   cfg.num_cus = d.num_cus;
   const bool keep = (flags & CBX_STEP_DISCARD_TASK_OUTPUTS) == 0;
   const cbx::Timing tm = {step_start_event(c, d, 0), step_stop_event(c, d, EV_A)};
-  // a clipped call in which no replica steps has nothing to clip: the plain kernel, the same bits
-  if (per_variable) HIP_TRY(cbx::launch_task_barrier_variables(a, d.var_tables_padded, keep, cfg, d.stream, tm));
+  // a clipped call in which no replica steps has nothing to clip: the per-variable or the plain kernel, the same bits
+  if (per_variable && !norms.empty())
+    HIP_TRY(cbx::launch_task_barrier_clipped_variables(a, d.var_tables_padded, records, keep, cfg, d.stream, tm));
+  else if (per_variable) HIP_TRY(cbx::launch_task_barrier_variables(a, d.var_tables_padded, keep, cfg, d.stream, tm));
   else if (!norms.empty()) HIP_TRY(cbx::launch_task_barrier_clipped(a, records, keep, cfg, d.stream, tm));
   else HIP_TRY(cbx::launch_task_barrier(a, keep, cfg, d.stream, tm));
   close_fused_step(c, d);
@@ -871,6 +881,11 @@ int cbx_step_and_synchronise_variables(cbx_context *c, int first, int clock, int
 int cbx_step_and_synchronise_clipped(cbx_context *c, int first, int clock, int autotune, const int *tasks,
                                      void *const *streams, unsigned flags) {
   return step_and_synchronise(c, first, clock, autotune, tasks, streams, flags, FusedClipped);
+}
+
+int cbx_step_and_synchronise_clipped_variables(cbx_context *c, int first, int clock, int autotune, const int *tasks,
+                                               void *const *streams, unsigned flags) {
+  return step_and_synchronise(c, first, clock, autotune, tasks, streams, flags, FusedClippedVariables);
 }
 
 int cbx_unlock_any(cbx_context *c) {

@@ -499,9 +499,13 @@ int cbx_sma_plan_step(cbx_sma_plan *p, void *const *streams, float *const *z, fl
 // cbx_sma_plan_step_and_optimise_clipped, with every stepping replica's norm
 // pass over its slot's scratch on streams[0] in front of the launch and the
 // clipped step inside it (task_barrier_clipped_kernels.hip).
+// SeamClippedVariables: cbx_sma_plan_step_and_optimise_clipped_variables, both:
+// the norm passes, then the kernel that clips and reads the plan's variable
+// table (task_barrier_clipped_variables_kernels.hip); when nobody steps, the
+// per-variable launch.
 namespace {
 int clip_slot(cbx_sma_plan *p, const char *what, int k, int slot, cbx::ClipScratch **out);
-enum SeamMode { SeamPlain, SeamVariables, SeamClipped };
+enum SeamMode { SeamPlain, SeamVariables, SeamClipped, SeamClippedVariables };
 struct SeamClip {
   const int *slot = nullptr;
   float max_norm = 0.0f;
@@ -515,10 +519,12 @@ static int plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *
                                   const int *step, const float *learning_rate, float alpha, float momentum,
                                   float replica_momentum, float weight_decay, int first, unsigned flags,
                                   SeamMode mode, const SeamClip &clip = SeamClip()) {
-  const bool variables = mode == SeamVariables, clipped = mode == SeamClipped;
-  const char *me = clipped     ? "cbx_sma_plan_step_and_optimise_clipped"
-                   : variables ? "cbx_sma_plan_step_and_optimise_variables"
-                               : "cbx_sma_plan_step_and_optimise";
+  const bool variables = mode == SeamVariables || mode == SeamClippedVariables;
+  const bool clipped = mode == SeamClipped || mode == SeamClippedVariables;
+  const char *me = mode == SeamClippedVariables ? "cbx_sma_plan_step_and_optimise_clipped_variables"
+                   : clipped                    ? "cbx_sma_plan_step_and_optimise_clipped"
+                   : variables                  ? "cbx_sma_plan_step_and_optimise_variables"
+                                                : "cbx_sma_plan_step_and_optimise";
   TraceRange trace(me);
   if (!p) return fail(CBX_ERR_INVALID, "null plan");
   if (variables && p->var_bounds.empty()) return fail(CBX_ERR_STATE, "%s before cbx_sma_plan_set_variables", me);
@@ -621,8 +627,12 @@ static int plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *
                                         static_cast<hipStream_t>(streams[0])));
       records.p[k] = cs[k]->record();
     }
-    HIP_TRY(cbx::launch_task_barrier_clipped(a, records, keep, cfg, static_cast<hipStream_t>(streams[0]),
-                                             p->next_timing()));
+    if (variables)
+      HIP_TRY(cbx::launch_task_barrier_clipped_variables(a, d.var_tables, records, keep, cfg,
+                                                         static_cast<hipStream_t>(streams[0]), p->next_timing()));
+    else
+      HIP_TRY(cbx::launch_task_barrier_clipped(a, records, keep, cfg, static_cast<hipStream_t>(streams[0]),
+                                               p->next_timing()));
   } else if (variables)
     HIP_TRY(cbx::launch_task_barrier_variables(a, d.var_tables, keep, cfg, static_cast<hipStream_t>(streams[0]),
                                                p->next_timing()));
@@ -664,6 +674,23 @@ int cbx_sma_plan_step_and_optimise_clipped(cbx_sma_plan *p, void *const *streams
   return plan_step_and_optimise(p, streams, z, last, nreplicas, replica_device, w, s, g, rlast, locked, copy, step,
                                 learning_rate, alpha, momentum, replica_momentum, weight_decay, first, flags,
                                 SeamClipped, clip);
+}
+
+int cbx_sma_plan_step_and_optimise_clipped_variables(cbx_sma_plan *p, void *const *streams, float *const *z,
+                                                     float *const *last, int nreplicas, const int *replica_device,
+                                                     float *const *w, float *const *s, float *const *g,
+                                                     float *const *rlast, const int *locked, const int *copy,
+                                                     const int *step, const float *learning_rate, const int *slot,
+                                                     float max_norm, int skip_nonfinite, float alpha, float momentum,
+                                                     float replica_momentum, float weight_decay, int first,
+                                                     unsigned flags) {
+  SeamClip clip;
+  clip.slot = slot;
+  clip.max_norm = max_norm;
+  clip.skip_nonfinite = skip_nonfinite;
+  return plan_step_and_optimise(p, streams, z, last, nreplicas, replica_device, w, s, g, rlast, locked, copy, step,
+                                learning_rate, alpha, momentum, replica_momentum, weight_decay, first, flags,
+                                SeamClippedVariables, clip);
 }
 
 // crossbowSynchronisationSynchronousSGD (synch/synchronoussgd.c:13-106) over

@@ -1,4 +1,4 @@
-// task_barrier_body.inc -- the body of the three fused task-step barrier
+// task_barrier_body.inc -- the body of the four fused task-step barrier
 // kernels, included inside each of them behind its step policy `step`
 // (task_barrier_step.h).  It is shared as text and not as a function: behind a
 // call, even an inlined one, the compiler schedules the kernels differently,

@@ -54,21 +54,8 @@ struct ClippedLauncher {
 
 hipError_t launch_task_barrier_clipped(const TaskBarrierArgs &a, const ClipRecordPtrs &rec, bool keep_task_outputs,
                                        const LaunchConfig &cfg, hipStream_t stream, Timing t) {
-  if (a.nrep < 1 || a.nrep > kMaxReplicas) return hipErrorInvalidValue;
-  // No record pointer is followed that the caller did not give: every stepping
-  // replica has one, and a launch without a stepping replica has nothing to
-  // clip (launch_task_barrier runs it).  The entries of the replicas that only
-  // join are loaded and not used: they take the first stepping replica's.
-  if (a.step_mask == 0) return hipErrorInvalidValue;
   ClipRecordPtrs full;
-  const ClipRecord *any = nullptr;
-  for (int k = 0; k < a.nrep; ++k) {
-    if (((a.step_mask >> k) & 1ull) == 0) continue;
-    if (!rec.p[k] || (reinterpret_cast<uintptr_t>(rec.p[k]) & 7u) != 0) return hipErrorInvalidValue;
-    if (!any) any = rec.p[k];
-  }
-  for (int k = 0; k < kMaxReplicas; ++k)
-    full.p[k] = (k < a.nrep && ((a.step_mask >> k) & 1ull) != 0) ? rec.p[k] : any;
+  if (!task_barrier_fill_records(a, rec, full)) return hipErrorInvalidValue;
   return task_barrier_launch(ClippedLauncher{full}, a, keep_task_outputs, cfg, stream, t);
 }
 

@@ -1,7 +1,8 @@
-// task_barrier_launch.h -- the host side the three fused task-step barrier
+// task_barrier_launch.h -- the host side the four fused task-step barrier
 // launches share (launch_task_barrier, launch_task_barrier_variables,
-// launch_task_barrier_clipped): the launch check, the grid, and the ladders
-// from the run-time arguments to one kernel instantiation.
+// launch_task_barrier_clipped, launch_task_barrier_clipped_variables): the
+// launch check, the grid, the ladders from the run-time arguments to one kernel
+// instantiation, and the checks of the tables and the records.
 //
 // Each object gives a launcher L:
 //   L::Step                         its step policy (task_barrier_step.h)
@@ -15,12 +16,43 @@
 // Any shape that is not compiled is hipErrorInvalidValue, before the launch.
 #pragma once
 
+#include "clip_internal.h"
+#include "optimise_plan.h"
 #include "sma_internal.h"
 #include "stream_helpers.h"
 
 namespace cbx {
 
 static_assert(kMaxReplicas <= 64, "step_mask holds one bit per replica");
+
+// The per-variable launches: no table is read past its end.  One entry per
+// 256-float chunk of the bulk, and every tail float has a variable.
+inline bool task_barrier_tables_cover(const TaskBarrierArgs &a, const VarTables &vt) {
+  if (!vt.chunks || !vt.bounds || !vt.mult || vt.nvars == 0 || a.n4 < 0 || a.tail_lo < 0) return false;
+  const uint64_t nchunks = ((uint64_t)vt.elements + kOptChunk - 1) / kOptChunk;
+  if ((uint64_t)a.n4 * 4u > nchunks * kOptChunk) return false;
+  if (a.tail_hi > a.tail_lo && a.tail_hi > (int64_t)vt.elements) return false;
+  return true;
+}
+
+// The clipped launches: no record pointer is followed that the caller did not
+// give.  Every stepping replica has one, 8-byte aligned (record_words), and a
+// launch without a stepping replica has nothing to clip (launch_task_barrier
+// runs it).  The entries of the replicas that only join are loaded and not
+// used: in `full` they take the first stepping replica's.
+inline bool task_barrier_fill_records(const TaskBarrierArgs &a, const ClipRecordPtrs &rec, ClipRecordPtrs &full) {
+  if (a.nrep < 1 || a.nrep > kMaxReplicas) return false;
+  if (a.step_mask == 0) return false;
+  const ClipRecord *any = nullptr;
+  for (int k = 0; k < a.nrep; ++k) {
+    if (((a.step_mask >> k) & 1ull) == 0) continue;
+    if (!rec.p[k] || (reinterpret_cast<uintptr_t>(rec.p[k]) & 7u) != 0) return false;
+    if (!any) any = rec.p[k];
+  }
+  for (int k = 0; k < kMaxReplicas; ++k)
+    full.p[k] = (k < a.nrep && ((a.step_mask >> k) & 1ull) != 0) ? rec.p[k] : any;
+  return true;
+}
 
 template <class L, bool MIXED, bool MOM, bool BMOM, bool WD, int P, bool TAIL, int U>
 constexpr bool task_barrier_compiled() {

@@ -1,13 +1,15 @@
-// task_barrier_step.h -- what the three fused task-step barrier kernels differ
+// task_barrier_step.h -- what the four fused task-step barrier kernels differ
 // in (task_barrier_kernels.hip, task_barrier_variables_kernels.hip,
-// task_barrier_clipped_kernels.hip), and the element-wise tail they share.
-// Device code only; the bulk of the kernels is task_barrier_body.inc.
+// task_barrier_clipped_kernels.hip, task_barrier_clipped_variables_kernels.hip),
+// and the element-wise tail they share.  Device code only; the bulk of the
+// kernels is task_barrier_body.inc.
 //
 // A step policy is a mode's two constants and the kernel parameters it has
 // beside TaskBarrierArgs.  The shared text reads a policy's members only under
 // `if constexpr` on its constants, so an instantiation holds nothing of a mode
-// it is not.  A kernel that is both (a learning rate per variable and clipped)
-// would be a fourth policy with both constants set and both sets of members.
+// it is not.  The kernel that is both (a learning rate per variable and
+// clipped) is the fourth policy, with both constants set and both sets of
+// members.
 #pragma once
 
 #include <cstddef>
@@ -44,6 +46,18 @@ struct VariablesStep {
 // record as well (launch_task_barrier_clipped).
 struct ClippedStep {
   static constexpr bool kPerVariable = false, kClips = true;
+  const ClipRecordPtrs &rec;
+};
+
+// Both: g = scale_i * g before weight decay, then the step with r_iv = a.rate[i]
+// * mult[v]; the skip and the kept g are ClippedStep's
+// (launch_sma_optimise_variables_clipped per replica, clip_internal.h).
+struct ClippedVariablesStep {
+  static constexpr bool kPerVariable = true, kClips = true;
+  const uint32_t *__restrict__ chunks;
+  const uint32_t *__restrict__ bounds;
+  const float *__restrict__ mult;
+  uint32_t nvars;
   const ClipRecordPtrs &rec;
 };
 

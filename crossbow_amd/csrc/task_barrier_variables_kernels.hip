@@ -60,12 +60,7 @@ struct VariablesLauncher {
 
 hipError_t launch_task_barrier_variables(const TaskBarrierArgs &a, const VarTables &vt, bool keep_task_outputs,
                                          const LaunchConfig &cfg, hipStream_t stream, Timing t) {
-  // No table is read past its end: one entry per 256-float chunk of the bulk,
-  // and every tail float has a variable.
-  if (!vt.chunks || !vt.bounds || !vt.mult || vt.nvars == 0 || a.n4 < 0 || a.tail_lo < 0) return hipErrorInvalidValue;
-  const uint64_t nchunks = ((uint64_t)vt.elements + kOptChunk - 1) / kOptChunk;
-  if ((uint64_t)a.n4 * 4u > nchunks * kOptChunk) return hipErrorInvalidValue;
-  if (a.tail_hi > a.tail_lo && a.tail_hi > (int64_t)vt.elements) return hipErrorInvalidValue;
+  if (!task_barrier_tables_cover(a, vt)) return hipErrorInvalidValue;
   return task_barrier_launch(VariablesLauncher{vt}, a, keep_task_outputs, cfg, stream, t);
 }
 

@@ -119,6 +119,19 @@ class SmaPlan:
                                        (_ints(slots) if slots is not None else None, ctypes.c_float(max_norm),
                                         1 if skip_nonfinite else 0))
 
+    def step_and_optimise_clipped_variables(self, streams, z, last, replicas, alpha: float, momentum: float,
+                                            replica_momentum: float, weight_decay: float, first: int = 0,
+                                            flags: int = 0, slots: Optional[Sequence[int]] = None,
+                                            max_norm: float = 0.0, skip_nonfinite: bool = False) -> int:
+        """``step_and_optimise_clipped`` with a learning rate per variable
+        (``cbx_sma_plan_step_and_optimise_clipped_variables``): the clipped
+        step at ``learning_rate * multipliers[v]`` of the table
+        ``set_variables`` installed.  Same arguments."""
+        return self._step_and_optimise("cbx_sma_plan_step_and_optimise_clipped_variables", streams, z, last, replicas,
+                                       alpha, momentum, replica_momentum, weight_decay, first, flags,
+                                       (_ints(slots) if slots is not None else None, ctypes.c_float(max_norm),
+                                        1 if skip_nonfinite else 0))
+
     def _step_and_optimise(self, name, streams, z, last, replicas, alpha, momentum, replica_momentum, weight_decay,
                            first, flags, clip=()) -> int:
         rate = (ctypes.c_float * max(1, len(replicas)))(*[float(r[8]) for r in replicas])

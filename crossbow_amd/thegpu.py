@@ -232,6 +232,17 @@ class TheGPU:
         return self._step_and_synchronise(self._L.cbx_step_and_synchronise_clipped, first, clock, autotune, tasks,
                                           streams, flags)
 
+    def step_and_synchronise_clipped_variables(self, first: int, clock: int, autotune: int, tasks: Sequence[int],
+                                               streams: Optional[Sequence[Optional[int]]] = None,
+                                               flags: int = 0) -> int:
+        """``cbx_step_and_synchronise_clipped_variables``:
+        ``step_and_synchronise`` with gradient clipping on and per-variable
+        learning rates at once, which each of the other three calls refuses.
+        Same arguments; with one of the two off it is the call for the other,
+        with both off that call."""
+        return self._step_and_synchronise(self._L.cbx_step_and_synchronise_clipped_variables, first, clock, autotune,
+                                          tasks, streams, flags)
+
     def _step_and_synchronise(self, fn, first, clock, autotune, tasks, streams, flags) -> int:
         tasks = list(tasks)
         N = self.num_replicas()

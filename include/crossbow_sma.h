@@ -283,9 +283,9 @@ int cbx_step_and_synchronise_variables (cbx_context *ctx, int first, int clock, 
  * pass.  Same parameters, same checks and refusals in the same order and before
  * the first side effect, except that clipping is honoured, not refused.
  * cbx_set_variable_learning_rates on with a multiplier that is not 1 stays
- * CBX_ERR_UNSUPPORTED: the clipped step with a rate per variable is not fused,
- * take cbx_replica_optimise and cbx_synchronise.  A refused call launches no
- * norm pass and bumps no counter of any record.
+ * CBX_ERR_UNSUPPORTED in this call: take
+ * cbx_step_and_synchronise_clipped_variables below.  A refused call launches
+ * no norm pass and bumps no counter of any record.
  *
  * The norm.  For every stepping replica, in id order, the norm pass and its
  * reduce (the launches cbx_replica_optimise makes) go on streams[id] where
@@ -318,6 +318,48 @@ int cbx_step_and_synchronise_variables (cbx_context *ctx, int first, int clock, 
  * same bits, and no launch for the norm.                                    */
 int cbx_step_and_synchronise_clipped (cbx_context *ctx, int first, int clock, int autotune,
                                       const int *tasks, void *const *streams, unsigned flags);
+/* cbx_step_and_synchronise with gradient clipping on (cbx_set_gradient_clip)
+ * and per-variable learning rates (cbx_set_variable_learning_rates on and a
+ * multiplier that is not 1) at once.  Same parameters, same checks and
+ * refusals in the same order and before the first side effect, except that
+ * neither of the two is refused.  A model whose variables do not tile its
+ * elements, a padded model too large for the chunk table and a stepping replica
+ * without clip scratch stay refused.  A refused call launches no norm pass and
+ * bumps no counter of any record.
+ *
+ * The norm passes are cbx_step_and_synchronise_clipped's: per stepping replica
+ * in id order on streams[id] where given, else on the sync stream, in front of
+ * the fused launch.
+ *
+ * The arithmetic.  Per element of variable v and per stepping replica i, one
+ * fp32 operation each:
+ *   g = scale_i * g                      the record's scale, before weight decay
+ *   g = fma (wd, w, g)                   (wd > 0)
+ *   s = w
+ *   r_iv = rate_i * mult[v]              rate_i = -lr_i
+ *   g = r_iv * g; g = fma (mu, last_i, g); last_i = g; w' = fma (1, g, w)   (momentum)
+ *   w' = fma (r_iv, g, w)                                                   (none)
+ * With the record's skip bit, s_i = w_i is a bit copy and w_i, g_i and last_i
+ * keep every bit.  Skipped wins over clipped.  A kept g_i is always written.
+ * Then the barrier of cbx_step_and_synchronise for every participating replica,
+ * Phase D in the same launch.
+ *
+ * The contract.  With flags == 0, z, the base `last`, every replica's w, s, g
+ * and `last`, every replica's cbx_clip_stats record and every piece of host
+ * state are left bit for bit as after
+ *   cbx_replica_optimise (ctx, id, tasks[id], streams[id])  (both on)
+ *                                     for every id with tasks[id] >= 0, in id order,
+ *   cbx_synchronise (ctx, first, clock, autotune, 0).
+ * With CBX_STEP_DISCARD_TASK_OUTPUTS, s_i and g_i of the stepping replicas are
+ * not written.
+ *
+ * With clipping on and every multiplier 1 (or variable rates off) the call is
+ * cbx_step_and_synchronise_clipped; with clipping off it is
+ * cbx_step_and_synchronise_variables; with both off, cbx_step_and_synchronise:
+ * the same kernel, the same bits.  When no replica steps there is no norm pass
+ * and no record is touched.                                                 */
+int cbx_step_and_synchronise_clipped_variables (cbx_context *ctx, int first, int clock, int autotune,
+                                                const int *tasks, void *const *streams, unsigned flags);
 /* TheGPU.unlockAny() GPU.c:1142-1149 -> modelmanager.c:233-245           */
 int cbx_unlock_any (cbx_context *ctx);
 
@@ -1058,6 +1100,33 @@ int cbx_sma_plan_step_and_optimise_clipped (cbx_sma_plan *plan, void *const *str
                                             const int *slot, float max_norm, int skip_nonfinite,
                                             float alpha, float momentum, float replica_momentum,
                                             float weight_decay, int first, unsigned flags);
+/* cbx_sma_plan_step_and_optimise_clipped with a learning rate per variable:
+ * stepping replica id clips through the record of slot[id] and steps variable v
+ * with r = (-learning_rate[id]) * multipliers[v] over the table that
+ * cbx_sma_plan_set_variables installed (CBX_ERR_STATE without one, before any
+ * other check but the NULL plan).  Parameters, checks and refusals are
+ * cbx_sma_plan_step_and_optimise_clipped's, the arithmetic
+ * cbx_step_and_synchronise_clipped_variables'.  With flags == 0 every buffer
+ * and every slot's record is left bit for bit as after
+ *   cbx_sma_plan_optimise_clipped (plan, 0, slot[id], streams[0], w[id], g[id],
+ *       rlast[id], s[id], learning_rate[id], replica_momentum, weight_decay,
+ *       max_norm, skip_nonfinite, 1)     for every id with step[id] != 0, in id order,
+ *   cbx_sma_plan_step (plan, streams, z, last, nreplicas, replica_device, w, s,
+ *       locked, copy, alpha, momentum, first);
+ * with CBX_STEP_DISCARD_TASK_OUTPUTS, s[id] and g[id] of the stepping replicas
+ * are not written.  When no replica steps the call is
+ * cbx_sma_plan_step_and_optimise_variables'.  Nothing at or past `elements` is
+ * read or written.                                                          */
+int cbx_sma_plan_step_and_optimise_clipped_variables (cbx_sma_plan *plan, void *const *streams,
+                                                      float *const *z, float *const *last,
+                                                      int nreplicas, const int *replica_device,
+                                                      float *const *w, float *const *s, float *const *g,
+                                                      float *const *rlast,
+                                                      const int *locked, const int *copy, const int *step,
+                                                      const float *learning_rate,
+                                                      const int *slot, float max_norm, int skip_nonfinite,
+                                                      float alpha, float momentum, float replica_momentum,
+                                                      float weight_decay, int first, unsigned flags);
 /* The statistics reduction of cbx_model_stats over caller-owned buffers of
  * exactly the plan's `elements` floats on the plan's device k (where a
  * Crossbow build would checksum, databuffer.c:141-162): `ref` against

@@ -9,9 +9,18 @@ N=tests/native
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O2 -std=c++17 -fPIC -shared -Wall \
   -Wl,-soname,libfakerccl.so -o "$N/libfakerccl.so.tmp" "$N/fake_rccl.cpp"
 mv "$N/libfakerccl.so.tmp" "$N/libfakerccl.so"
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wall -ffp-contract=off \
-  -I include -o "$N/libcrossbow_sma_fakerccl.so.tmp" \
-  crossbow_amd/csrc/context.hip crossbow_amd/csrc/sync_steps.hip crossbow_amd/csrc/sma_kernels.hip crossbow_amd/csrc/averaging_kernels.hip crossbow_amd/csrc/sma_seam.hip crossbow_amd/csrc/stats_kernels.hip crossbow_amd/csrc/variable_rate_kernels.hip crossbow_amd/csrc/clip_kernels.hip crossbow_amd/csrc/task_barrier_kernels.hip crossbow_amd/csrc/task_barrier_variables_kernels.hip crossbow_amd/csrc/task_barrier_clipped_kernels.hip \
+# One object per source, compiled side by side ($MAX_JOBS at a time, else one per CPU, 16 at the most), then one link.
+SRCS="crossbow_amd/csrc/context.hip crossbow_amd/csrc/sync_steps.hip crossbow_amd/csrc/sma_kernels.hip crossbow_amd/csrc/averaging_kernels.hip crossbow_amd/csrc/sma_seam.hip crossbow_amd/csrc/stats_kernels.hip crossbow_amd/csrc/variable_rate_kernels.hip crossbow_amd/csrc/clip_kernels.hip crossbow_amd/csrc/task_barrier_kernels.hip crossbow_amd/csrc/task_barrier_variables_kernels.hip crossbow_amd/csrc/task_barrier_clipped_kernels.hip crossbow_amd/csrc/task_barrier_clipped_variables_kernels.hip"
+JOBS=${MAX_JOBS:-$(nproc)}
+[ "$JOBS" -gt 16 ] && JOBS=16
+TMP=$(mktemp -d)
+trap 'rm -rf "$TMP"' EXIT
+export TMP
+printf '%s\n' $SRCS | xargs -P "$JOBS" -I{} sh -c \
+  '/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -ffp-contract=off \
+     -I include -c -o "$TMP/$(basename "$1" .hip).o" "$1"' sh {}
+OBJS=$(for f in $SRCS; do printf '%s ' "$TMP/$(basename "$f" .hip).o"; done)
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o "$N/libcrossbow_sma_fakerccl.so.tmp" $OBJS \
   -L "$N" -lfakerccl -Wl,-rpath,'$ORIGIN' -lrocprofiler-sdk-roctx -lpthread
 mv "$N/libcrossbow_sma_fakerccl.so.tmp" "$N/libcrossbow_sma_fakerccl.so"
 echo "built $N/libfakerccl.so $N/libcrossbow_sma_fakerccl.so"
