@@ -705,15 +705,9 @@ int cbx_synchronise_staged(cbx_context *c, int first, int clock, int autotune, i
 // other one launches.  Everything else is one code path.
 enum FusedMode { FusedPlain, FusedVariables, FusedClipped, FusedClippedVariables };
 
-static int step_and_synchronise(cbx_context *c, int first, int clock, int autotune, const int *tasks,
-                                void *const *streams, unsigned flags, FusedMode mode) {
-  const bool variables = mode == FusedVariables || mode == FusedClippedVariables;
-  const bool clips = mode == FusedClipped || mode == FusedClippedVariables;
-  const char *me = mode == FusedClippedVariables ? "cbx_step_and_synchronise_clipped_variables"
-                   : mode == FusedClipped        ? "cbx_step_and_synchronise_clipped"
-                   : variables                   ? "cbx_step_and_synchronise_variables"
-                                                 : "cbx_step_and_synchronise";
-  TraceRange trace(me);
+// What every fused call checks first, of its arguments and of the devices: the
+// same refusals in the same order for the SMA calls and the elastic one (`me`).
+static int check_fused_call(cbx_context *c, const char *me, int first, const int *tasks, unsigned flags) {
   TRY(check_manager_q(c));
   if (first < 0 || first > c->size) return fail(CBX_ERR_INVALID, "first replica %d out of range", first);
   if (!tasks) return fail(CBX_ERR_INVALID, "%s: null task list (one entry per replica: a task number, or -1)", me);
@@ -733,26 +727,16 @@ static int step_and_synchronise(cbx_context *c, int first, int clock, int autotu
                 "kernel A of the split path", me, c->G > 1 ? c->G : (int)c->devs.size());
   if (c->force_split)
     return fail(CBX_ERR_UNSUPPORTED, "%s: cbx_set_force_split is on; kernel A of the split path is not fused", me);
-  const int type = c->model.type;
-  if (type == CBX_UPDATE_SYNCHRONOUSEAMSGD && c->elastic_average)
-    return fail(CBX_ERR_UNSUPPORTED, "%s: elastic averaging is on (cbx_set_elastic_average); only the SMA barrier is fused", me);
-  if (type != CBX_UPDATE_SMA && type != CBX_UPDATE_SYNCHRONOUSEAMSGD)
-    return fail(CBX_ERR_UNSUPPORTED, "%s: update model %d; only SMA (7) and SYNCHRONOUSEAMSGD (3) are fused", me, type);
-  const bool clip = c->clip_on();
-  const bool per_variable = c->variable_rates && c->model.conf.irregular > 0;
-  if (clip && !clips)
-    return fail(CBX_ERR_UNSUPPORTED, "%s: gradient clipping is on; the clipped step needs its norm pass first, use %s, "
-                "or cbx_replica_optimise and cbx_synchronise", me,
-                per_variable ? "cbx_step_and_synchronise_clipped_variables" : "cbx_step_and_synchronise_clipped");
-  if (per_variable && !variables)
-    return fail(CBX_ERR_UNSUPPORTED, "%s: variable learning rates are on with %d irregular variables; use %s, or "
-                "cbx_replica_optimise and cbx_synchronise", me, c->model.conf.irregular,
-                clip ? "cbx_step_and_synchronise_clipped_variables" : "cbx_step_and_synchronise_variables");
-  if (per_variable && !c->var_refusal.empty())
-    return fail(CBX_ERR_UNSUPPORTED, "%s with variable learning rates: %s", me, c->var_refusal.c_str());
+  return CBX_OK;
+}
+
+// And last, once the call's own barrier and modes have passed: the stepping
+// replicas' configurations on the one device.  *ref_out is the first stepping
+// replica's (null: nobody steps); `clip`: every stepping replica needs its clip
+// scratch.
+static int check_stepping_replicas(cbx_context *c, const char *me, int first, const int *tasks, bool clip,
+                                   const SolverConf **ref_out) {
   Device &d = c->devs[0];
-  if (per_variable && !d.var_tables_padded.chunks)
-    return fail(CBX_ERR_UNSUPPORTED, "%s: the padded model is too large for the chunk table", me);
   const SolverConf *ref = nullptr;  // the first stepping replica's configuration
   int participating = 0;
   for (int id : d.replicas) {
@@ -779,6 +763,43 @@ static int step_and_synchronise(cbx_context *c, int first, int clock, int autotu
     return fail(CBX_ERR_UNSUPPORTED, "more than %d locked replicas on one device", cbx::kMaxReplicas);
   if (ref && ref->momentum > 0 && !c->has_last)
     return fail(CBX_ERR_STATE, "replica momentum without a `last` buffer (model.c:116-120)");
+  *ref_out = ref;
+  return CBX_OK;
+}
+
+static int step_and_synchronise(cbx_context *c, int first, int clock, int autotune, const int *tasks,
+                                void *const *streams, unsigned flags, FusedMode mode) {
+  const bool variables = mode == FusedVariables || mode == FusedClippedVariables;
+  const bool clips = mode == FusedClipped || mode == FusedClippedVariables;
+  const char *me = mode == FusedClippedVariables ? "cbx_step_and_synchronise_clipped_variables"
+                   : mode == FusedClipped        ? "cbx_step_and_synchronise_clipped"
+                   : variables                   ? "cbx_step_and_synchronise_variables"
+                                                 : "cbx_step_and_synchronise";
+  TraceRange trace(me);
+  TRY(check_fused_call(c, me, first, tasks, flags));
+  const int size = c->size;
+  const int type = c->model.type;
+  if (type == CBX_UPDATE_SYNCHRONOUSEAMSGD && c->elastic_average)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: elastic averaging is on (cbx_set_elastic_average); only the SMA barrier is fused", me);
+  if (type != CBX_UPDATE_SMA && type != CBX_UPDATE_SYNCHRONOUSEAMSGD)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: update model %d; only SMA (7) and SYNCHRONOUSEAMSGD (3) are fused", me, type);
+  const bool clip = c->clip_on();
+  const bool per_variable = c->variable_rates && c->model.conf.irregular > 0;
+  if (clip && !clips)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: gradient clipping is on; the clipped step needs its norm pass first, use %s, "
+                "or cbx_replica_optimise and cbx_synchronise", me,
+                per_variable ? "cbx_step_and_synchronise_clipped_variables" : "cbx_step_and_synchronise_clipped");
+  if (per_variable && !variables)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: variable learning rates are on with %d irregular variables; use %s, or "
+                "cbx_replica_optimise and cbx_synchronise", me, c->model.conf.irregular,
+                clip ? "cbx_step_and_synchronise_clipped_variables" : "cbx_step_and_synchronise_variables");
+  if (per_variable && !c->var_refusal.empty())
+    return fail(CBX_ERR_UNSUPPORTED, "%s with variable learning rates: %s", me, c->var_refusal.c_str());
+  Device &d = c->devs[0];
+  if (per_variable && !d.var_tables_padded.chunks)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: the padded model is too large for the chunk table", me);
+  const SolverConf *ref = nullptr;  // the first stepping replica's configuration (null: nobody steps)
+  TRY(check_stepping_replicas(c, me, first, tasks, clip, &ref));
 
   // The rates, in id order: a query may raise the replica's `_copy`
   // (solverconfiguration.c:133,147), which this same call's Phase D honours.
@@ -886,6 +907,86 @@ int cbx_step_and_synchronise_clipped(cbx_context *c, int first, int clock, int a
 int cbx_step_and_synchronise_clipped_variables(cbx_context *c, int first, int clock, int autotune, const int *tasks,
                                                void *const *streams, unsigned flags) {
   return step_and_synchronise(c, first, clock, autotune, tasks, streams, flags, FusedClippedVariables);
+}
+
+// The pending task steps of the locked replicas and the one-GPU
+// elastic-averaging barrier in one launch (task_elastic_kernels.hip): what
+// step_and_synchronise above is to the SMA barrier, for update model 3 with
+// cbx_set_elastic_average.  The same validation before the first side effect;
+// no clipped and no per-variable form, no base momentum, and no copy flag is
+// read or cleared (synchronouseamsgd.c:42-90 has no Phase D): a flag that a
+// rate query of this call raises stays raised, as after the two calls.  It ends
+// as averaging_step's fused form does.
+int cbx_step_and_synchronise_elastic(cbx_context *c, int first, int clock, int autotune, const int *tasks,
+                                     void *const *streams, unsigned flags) {
+  const char *me = "cbx_step_and_synchronise_elastic";
+  TraceRange trace(me);
+  TRY(check_fused_call(c, me, first, tasks, flags));
+  const int size = c->size;
+  const int type = c->model.type;
+  if ((type == CBX_UPDATE_SMA || type == CBX_UPDATE_SYNCHRONOUSEAMSGD) && !c->elastic_average)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: elastic averaging is off (cbx_set_elastic_average); the SMA barrier takes "
+                "cbx_step_and_synchronise", me);
+  if (type != CBX_UPDATE_SYNCHRONOUSEAMSGD)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: update model %d; only SYNCHRONOUSEAMSGD (3) with elastic averaging on is fused "
+                "here", me, type);
+  if (c->clip_on())
+    return fail(CBX_ERR_UNSUPPORTED, "%s: gradient clipping is on; use cbx_replica_optimise and cbx_synchronise", me);
+  if (c->variable_rates && c->model.conf.irregular > 0)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: variable learning rates are on with %d irregular variables; use "
+                "cbx_replica_optimise and cbx_synchronise", me, c->model.conf.irregular);
+  Device &d = c->devs[0];
+  const SolverConf *ref = nullptr;  // the first stepping replica's configuration (null: nobody steps)
+  TRY(check_stepping_replicas(c, me, first, tasks, false, &ref));
+
+  // The rates, in id order: a query may raise the replica's `_copy`
+  // (solverconfiguration.c:133,147), which this barrier leaves as it finds it.
+  std::vector<float> lr((size_t)size, 0.0f);
+  for (int id = 0; id < size; ++id)
+    if (tasks[id] >= 0) TRY(c->replicas[id]->conf.learning_rate(tasks[id], &lr[(size_t)id]));
+
+  cbx::TaskBarrierArgs a;
+  std::memset(&a, 0, sizeof(a));
+  int k = 0;
+  std::vector<hipStream_t> callers;
+  for (int id : d.replicas) {  // increasing id order, synchronouseamsgd.c:46
+    if (id < first || !c->locked[id]) continue;
+    Replica &r = *c->replicas[id];
+    a.w[k] = reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_DATA));
+    if (tasks[id] >= 0) {
+      a.step_mask |= 1ull << k;
+      a.s[k] = reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_DIFF));
+      a.g[k] = reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_GRADIENT));
+      a.last[k] = r.conf.momentum > 0 ? reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_LAST)) : nullptr;
+      a.rate[k] = -lr[(size_t)id];  // sma.cu:43
+      hipStream_t st = streams && streams[id] ? reinterpret_cast<hipStream_t>(streams[id]) : d.stream;
+      if (st != d.stream && std::find(callers.begin(), callers.end(), st) == callers.end()) callers.push_back(st);
+    }
+    ++k;
+  }
+  a.nrep = k;
+  a.z = reinterpret_cast<cbx::v4f *>(base_dev(c, d, CBX_BUF_DATA));
+  a.n4 = c->n4;
+  a.alpha = c->model.conf.alpha;  // synchronouseamsgd.c:13, theModel's conf
+  a.momentum = ref ? ref->momentum : 0.0f;
+  a.wd = ref ? ref->weightDecay : 0.0f;
+
+  // The launch comes after the gradients: one deferred wait per caller stream,
+  // queued now, as cbx_synchronise queues the task steps' (DESIGN.md 7).
+  HIP_TRY(hipSetDevice(d.hip_id));
+  if (!c->fault_skip_task_wait)
+    for (hipStream_t st : callers) TRY(defer_task_wait(d, st));
+  TRY(flush_task_waits(c));
+  // as cbx_synchronise counts a barrier that is not SMA's: its start is a marker of its own (step_start_event)
+  c->foreign_ops.fetch_add(1, std::memory_order_relaxed);
+
+  cbx::LaunchConfig cfg = c->task_barrier_cfg;
+  cfg.num_cus = d.num_cus;
+  const bool keep = (flags & CBX_STEP_DISCARD_TASK_OUTPUTS) == 0;
+  HIP_TRY(cbx::launch_task_elastic(a, keep, cfg, d.stream, {step_start_event(c, d, 0), step_stop_event(c, d, EV_A)}));
+  close_fused_step(c, d);  // the ring slot, cross_valid = false: averaging_step's fused form
+  TRY(finish_step(c));
+  return finish_barrier(c, clock, autotune);
 }
 
 int cbx_unlock_any(cbx_context *c) {

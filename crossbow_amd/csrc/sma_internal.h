@@ -394,6 +394,18 @@ inline LaunchConfig task_barrier_launch_config() {
   c.waves_per_cu = -1;
   return c;
 }
+// The replicas' pending task steps fused into the one-GPU elastic-averaging
+// barrier (cbx_step_and_synchronise_elastic, cbx_ea_plan_step_and_optimise;
+// task_elastic_kernels.hip, a shared object of its own:
+// libcrossbow_sma_elastic_steps.so): launch_sma_optimise on every replica whose
+// step_mask bit is set, then launch_averaging_fused(kElasticW), in one pass.
+// Of TaskBarrierArgs it reads no blast, no copy and no s of a replica that only
+// joins; a.momentum and a.wd are 0 when nobody steps.  Compiled forms: no tail
+// with unroll 1 or 2 and either policy; a tail with unroll 1 and policy 1.
+// Anything else is hipErrorInvalidValue, as is a block over 256.  The launch
+// shape is launch_task_barrier's (task_barrier_launch_config).
+hipError_t launch_task_elastic(const TaskBarrierArgs &a, bool keep_task_outputs, const LaunchConfig &cfg,
+                               hipStream_t stream, Timing t = {});
 // DEFAULT update model (0, kernels/optimisers/default.cu:3-131): the task
 // step moves the replica and its device's base model by the same gradient.
 // Reads w, g (, last), z; writes g (if changed), last, w, z.

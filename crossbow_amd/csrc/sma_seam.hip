@@ -693,6 +693,85 @@ int cbx_sma_plan_step_and_optimise_clipped_variables(cbx_sma_plan *p, void *cons
                                 SeamClippedVariables, clip);
 }
 
+// The task steps of kernels/optimisers/synchronouseamsgd.cu of every stepping
+// replica and the one-device elastic-averaging barrier
+// (synch/synchronouseamsgd.c:42-90) in one launch over the caller's buffers:
+// the context's cbx_step_and_synchronise_elastic (context.hip) with the
+// caller's rates and stream order.  No `last`, `copy` or base momentum: the
+// barrier has none.  The bulk runs the context's float4 loop, the elements past
+// it the kernel's TAIL workgroups (task_elastic_kernels.hip).  Everything is
+// validated before the launch; the plan queues no wait of its own.
+int cbx_ea_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *const *z, int nreplicas,
+                                  const int *replica_device, float *const *w, float *const *s, float *const *g,
+                                  float *const *rlast, const int *locked, const int *step, const float *learning_rate,
+                                  float alpha, float replica_momentum, float weight_decay, int first, unsigned flags) {
+  const char *me = "cbx_ea_plan_step_and_optimise";
+  TraceRange trace(me);
+  if (!p) return fail(CBX_ERR_INVALID, "null plan");
+  if (!streams || !z || nreplicas < 0 || (nreplicas > 0 && (!replica_device || !w || !locked || !step)))
+    return fail(CBX_ERR_INVALID, "%s: missing arguments", me);
+  if (flags & ~CBX_STEP_DISCARD_TASK_OUTPUTS) return fail(CBX_ERR_INVALID, "%s: unknown flag bits 0x%x", me, flags);
+  if (first < 0 || first > nreplicas) return fail(CBX_ERR_INVALID, "%s: first replica %d out of range", me, first);
+  const bool keep = (flags & CBX_STEP_DISCARD_TASK_OUTPUTS) == 0;
+  const bool rmom = replica_momentum > 0.0f;  // sma.cu:45
+  for (int id = 0; id < nreplicas; ++id) {
+    if (!step[id]) continue;
+    if (!locked[id]) return fail(CBX_ERR_INVALID, "%s: stepping replica %d is not locked for this barrier", me, id);
+    if (id < first) return fail(CBX_ERR_INVALID, "%s: stepping replica %d is below the first replica %d", me, id, first);
+    if (!g || !learning_rate) return fail(CBX_ERR_INVALID, "%s: a stepping replica needs g and learning_rate", me);
+    if (keep && !s) return fail(CBX_ERR_INVALID, "%s: a stepping replica whose outputs are kept needs s", me);
+    if (rmom && !rlast) return fail(CBX_ERR_INVALID, "%s: replica momentum > 0 needs the replicas' last buffers", me);
+  }
+  if (p->devs.size() != 1 || p->ranks != 1)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: a plan of %d devices and %d ranks; the task steps are fused into the one-GPU "
+                "barrier only, not into kernel A of the split path", me, (int)p->devs.size(), p->ranks);
+  if (!z[0] || !aligned16(z[0])) return fail(CBX_ERR_INVALID, "%s: base buffers must be non-null and 16-byte aligned", me);
+  cbx::TaskBarrierArgs a;
+  std::memset(&a, 0, sizeof(a));
+  int participating = 0;
+  bool steps = false;
+  for (int id = first; id < nreplicas; ++id) {  // increasing id order, synchronouseamsgd.c:46
+    if (!locked[id]) continue;
+    if (replica_device[id] != 0) return fail(CBX_ERR_INVALID, "%s: replica %d on device %d of 1", me, id, replica_device[id]);
+    const bool st = step[id] != 0;
+    if (!w[id] || !aligned16(w[id])) return fail(CBX_ERR_INVALID, "%s: replica %d: w must be non-null and 16-byte aligned", me, id);
+    // s is only written, by a stepping replica whose outputs are kept
+    if (st && keep && (!s[id] || !aligned16(s[id])))
+      return fail(CBX_ERR_INVALID, "%s: stepping replica %d: s must be non-null and 16-byte aligned", me, id);
+    if (st && (!g[id] || !aligned16(g[id])))
+      return fail(CBX_ERR_INVALID, "%s: stepping replica %d: g must be non-null and 16-byte aligned", me, id);
+    if (st && rmom && (!rlast[id] || !aligned16(rlast[id])))
+      return fail(CBX_ERR_INVALID, "%s: stepping replica %d: replica momentum > 0 needs a 16-byte aligned last buffer", me, id);
+    if (++participating > cbx::kMaxReplicas) continue;  // counted on, refused below
+    const int k = a.nrep++;
+    a.w[k] = reinterpret_cast<cbx::v4f *>(w[id]);
+    if (st) {
+      steps = true;
+      a.step_mask |= 1ull << k;
+      a.s[k] = keep ? reinterpret_cast<cbx::v4f *>(s[id]) : nullptr;
+      a.g[k] = reinterpret_cast<cbx::v4f *>(g[id]);
+      a.last[k] = rmom ? reinterpret_cast<cbx::v4f *>(rlast[id]) : nullptr;
+      a.rate[k] = -1.0f * learning_rate[id];  // sma.cu:43
+    }
+  }
+  if (participating > cbx::kMaxReplicas)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: %d participating replicas, more than %d on one device", me, participating,
+                cbx::kMaxReplicas);
+  a.z = reinterpret_cast<cbx::v4f *>(z[0]);
+  a.n4 = p->n4b;
+  a.alpha = alpha;  // synchronouseamsgd.c:13
+  a.momentum = steps && rmom ? replica_momentum : 0.0f;
+  a.wd = steps && weight_decay > 0.0f ? weight_decay : 0.0f;
+  a.tail_lo = p->n4b * 4;  // the elements past the last whole chunk ride the same launch
+  a.tail_hi = p->n;
+  auto &d = p->devs[0];
+  HIP_TRY(hipSetDevice(d.hip_id));
+  cbx::LaunchConfig cfg = p->task_barrier_cfg;
+  cfg.num_cus = d.num_cus;
+  HIP_TRY(cbx::launch_task_elastic(a, keep, cfg, static_cast<hipStream_t>(streams[0]), p->next_timing()));
+  return CBX_OK;
+}
+
 // crossbowSynchronisationSynchronousSGD (synch/synchronoussgd.c:13-106) over
 // the caller's buffers: the all-reduce of every device's accumulated,
 // lr-scaled gradient, the 1/wpc scale, the base momentum (the configured one,

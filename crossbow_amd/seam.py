@@ -164,6 +164,26 @@ class SmaPlan:
             _ptrs([r[1] for r in replicas]), _ptrs(s) if any(s) else None, _ints([r[3] for r in replicas]),
             ctypes.c_float(alpha), first), "cbx_ea_plan_step")
 
+    def elastic_step_and_optimise(self, streams: Sequence[int], z: Sequence[int],
+                                  replicas: Sequence[Tuple[int, int, Optional[int], Optional[int], Optional[int], int,
+                                                           int, float]],
+                                  alpha: float, replica_momentum: float, weight_decay: float, first: int = 0,
+                                  flags: int = 0) -> None:
+        """The stepping replicas' task steps and the elastic-averaging barrier
+        in one launch (``cbx_ea_plan_step_and_optimise``; one device, one
+        rank).  ``replicas[id]`` = (device index, w, s, g, rlast, locked, step,
+        learning_rate), as for ``step_and_optimise`` without ``copy``; ``s``
+        may be None for a replica that only joins, or that steps under
+        ``STEP_DISCARD_TASK_OUTPUTS``.  The caller orders ``streams[0]`` behind
+        the gradients."""
+        rate = (ctypes.c_float * max(1, len(replicas)))(*[float(r[7]) for r in replicas])
+        _raise(self.lib, self.lib.cbx_ea_plan_step_and_optimise(
+            self._p, _ptrs(streams), _ptrs(z), len(replicas), _ints([r[0] for r in replicas]),
+            _ptrs([r[1] for r in replicas]), _ptrs([r[2] for r in replicas]), _ptrs([r[3] for r in replicas]),
+            _ptrs([r[4] for r in replicas]), _ints([r[5] for r in replicas]), _ints([r[6] for r in replicas]), rate,
+            ctypes.c_float(alpha), ctypes.c_float(replica_momentum), ctypes.c_float(weight_decay), first,
+            ctypes.c_uint(flags)), "cbx_ea_plan_step_and_optimise")
+
     def polyak_step(self, streams: Sequence[int], z: Sequence[int], last: Optional[Sequence[Optional[int]]],
                     replicas: Sequence[Tuple[int, int, int, int]], alpha: float, clock: int, first: int = 0) -> int:
         """One Polyak-Ruppert barrier (``cbx_pr_plan_step``).  ``replicas[id]`` =

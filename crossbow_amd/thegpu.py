@@ -243,6 +243,16 @@ class TheGPU:
         return self._step_and_synchronise(self._L.cbx_step_and_synchronise_clipped_variables, first, clock, autotune,
                                           tasks, streams, flags)
 
+    def step_and_synchronise_elastic(self, first: int, clock: int, autotune: int, tasks: Sequence[int],
+                                     streams: Optional[Sequence[Optional[int]]] = None, flags: int = 0) -> int:
+        """``cbx_step_and_synchronise_elastic``: ``step_and_synchronise`` for
+        EA-SGD (update model 3 with ``set_elastic_average``), which that call
+        refuses: the pending task steps and the one-GPU elastic-averaging
+        barrier in one launch.  Same arguments; no copy flag is read or
+        cleared, and the base model's ``last`` is not touched."""
+        return self._step_and_synchronise(self._L.cbx_step_and_synchronise_elastic, first, clock, autotune, tasks,
+                                          streams, flags)
+
     def _step_and_synchronise(self, fn, first, clock, autotune, tasks, streams, flags) -> int:
         tasks = list(tasks)
         N = self.num_replicas()

@@ -244,7 +244,8 @@ int cbx_synchronise_staged (cbx_context *ctx, int first, int clock, int autotune
  * momentum on a stepping replica; stepping replicas whose momentum or weight
  * decay differ.  CBX_ERR_STATE: replica momentum without a `last` buffer.
  * A model with per-variable rates takes cbx_step_and_synchronise_variables
- * below; this call keeps its refusal.                                      */
+ * below, elastic averaging cbx_step_and_synchronise_elastic; this call keeps
+ * its refusals.                                                            */
 #define CBX_STEP_DISCARD_TASK_OUTPUTS 1u
 int cbx_step_and_synchronise (cbx_context *ctx, int first, int clock, int autotune,
                               const int *tasks, void *const *streams, unsigned flags);
@@ -360,6 +361,54 @@ int cbx_step_and_synchronise_clipped (cbx_context *ctx, int first, int clock, in
  * and no record is touched.                                                 */
 int cbx_step_and_synchronise_clipped_variables (cbx_context *ctx, int first, int clock, int autotune,
                                                 const int *tasks, void *const *streams, unsigned flags);
+/* The pending task steps of the locked replicas and the one-GPU
+ * elastic-averaging barrier in one launch: cbx_step_and_synchronise for EA-SGD
+ * (update model SYNCHRONOUSEAMSGD (3) with cbx_set_elastic_average on; the
+ * reference's ELASTIC_AVERAGE build, kernels/optimisers/synchronouseamsgd.cu
+ * and synch/synchronouseamsgd.c:42-90), which the four calls above refuse.
+ * Same parameters: tasks[id] is replica id's task number, or -1 when it only
+ * joins the barrier; streams[id] the stream its gradient was produced on (NULL:
+ * the sync stream), behind which the launch is ordered.  Asynchronous.
+ *
+ * The arithmetic.  Per element and per participating replica i (locked, id >=
+ * first) in ascending id order, one fp32 operation per reference call:
+ *   stepping (tasks[id] >= 0), rate_i = -learning_rate (conf_i, tasks[id]):
+ *     g = fma (wd, w, g)                                            (wd > 0)
+ *     s = w                                                         (outputs kept)
+ *     g = rate_i * g; g = fma (mu, last_i, g); last_i = g; w' = fma (1, g, w)   (mu > 0)
+ *     w' = fma (rate_i, g, w)                                                   (mu = 0)
+ *   only joining: w' = w_i
+ *   all: d = fma (-1, z, w'); w_i = fma (-alpha, d, w'); acc = fma (alpha, d, acc)
+ * then z = fma (1, acc, z), acc starting from +0.  d is taken from the stepped
+ * w', not from a snapshot; there is no base momentum (the base `last` is not
+ * touched) and no Phase D: copy flags are neither read nor cleared, so a
+ * learning-rate query of this call that raises a replica's copy flag
+ * (MULTISTEP at its boundary) leaves it raised, as the sequence does.
+ *
+ * The contract.  With flags == 0 the call leaves every buffer (z, every w_i,
+ * last_i, s_i and g_i) bit for bit, and every piece of host state (copy flags,
+ * clocks, `updates`, the step event, one timing-history entry), as if the
+ * caller had made
+ *   cbx_replica_optimise (ctx, id, tasks[id], streams[id])  for every id with
+ *                                                           tasks[id] >= 0,
+ *   cbx_synchronise (ctx, first, clock, autotune, 0).
+ * With CBX_STEP_DISCARD_TASK_OUTPUTS, s_i and g_i of the stepping replicas are
+ * not written at all; this barrier never reads s_i, so the promise that goes
+ * with the flag is only that nobody else reads them before the replica steps
+ * again.  When nobody steps the call is cbx_synchronise under elastic averaging.
+ *
+ * Everything is checked before the first side effect: a refused call changes
+ * no buffer, flag or clock, and cbx_last_error names the cause.
+ * CBX_ERR_INVALID: as cbx_step_and_synchronise.  CBX_ERR_UNSUPPORTED: more than
+ * one device, or cbx_set_force_split on; an update model other than
+ * SYNCHRONOUSEAMSGD (3) with elastic averaging on (plain SMA takes
+ * cbx_step_and_synchronise); gradient clipping on;
+ * cbx_set_variable_learning_rates on with a multiplier that is not 1; Nesterov
+ * momentum on a stepping replica; stepping replicas whose momentum or weight
+ * decay differ.  CBX_ERR_STATE: replica momentum without a `last` buffer.
+ * The launch shape is cbx_set_task_barrier_kernel_config's.                 */
+int cbx_step_and_synchronise_elastic (cbx_context *ctx, int first, int clock, int autotune,
+                                      const int *tasks, void *const *streams, unsigned flags);
 /* TheGPU.unlockAny() GPU.c:1142-1149 -> modelmanager.c:233-245           */
 int cbx_unlock_any (cbx_context *ctx);
 
@@ -1251,6 +1300,41 @@ int cbx_ssgd_accumulate_buffers (void *stream, const float *w, float *g, float *
 int cbx_ea_plan_step (cbx_sma_plan *plan, void *const *streams, float *const *z, int nreplicas,
                       const int *replica_device, float *const *w, const float *const *s, const int *locked,
                       float alpha, int first);
+/* The stepping replicas' task steps (kernels/optimisers/synchronouseamsgd.cu)
+ * and the one-device elastic-averaging barrier (synch/synchronouseamsgd.c:42-90)
+ * in one launch over the caller's buffers of exactly `elements` floats: what
+ * cbx_step_and_synchronise_elastic is to a context, for a tau = 1 EA-SGD build.
+ * It moves (28R + 8) n bytes, or (20R + 8) n with the discard flag, where the
+ * two calls move (36R + 8) n.  Arguments named as for
+ * cbx_sma_plan_step_and_optimise mean the same; there is no `last`, no `copy`
+ * and no base momentum, as the barrier has none.  s[id] may be NULL for a
+ * replica that only joins (the barrier reads no snapshot on one device) and for
+ * one that steps under CBX_STEP_DISCARD_TASK_OUTPUTS; `s` itself may be NULL
+ * when every s[id] may.
+ * The contract.  With flags == 0 every buffer (z, every w, rlast, s and g) is
+ * left bit for bit as after
+ *   cbx_sma_optimise_buffers (streams[0], w[id], g[id], rlast[id], s[id],
+ *       elements, learning_rate[id], replica_momentum, weight_decay)
+ *                                 for every id with step[id] != 0, in id order,
+ *   cbx_ea_plan_step (plan, streams, z, nreplicas, replica_device, w, NULL,
+ *       locked, alpha, first)     on a one-device, one-rank plan.
+ * With the discard flag, s[id] and g[id] of the stepping replicas are not
+ * written.  Nothing at or past `elements` is read or written: the last elements
+ * ride the same launch on extra workgroups in front.  One launch on streams[0],
+ * asynchronous; the caller orders streams[0] behind the gradients.  With
+ * cbx_sma_plan_set_timing on, the launch stamps itself into the plan's ring.
+ * Everything is checked before the launch, as in cbx_sma_plan_step_and_optimise:
+ * CBX_ERR_INVALID for a missing argument, an unknown flag bit, `first` out of
+ * range, a stepping replica that is not locked or below `first`, a participating
+ * replica on a device other than 0 or with a missing or misaligned buffer;
+ * CBX_ERR_UNSUPPORTED for a plan with more than one device or rank, and for
+ * more than 64 participating replicas.  Returns CBX_OK or an error.        */
+int cbx_ea_plan_step_and_optimise (cbx_sma_plan *plan, void *const *streams, float *const *z,
+                                   int nreplicas, const int *replica_device,
+                                   float *const *w, float *const *s, float *const *g, float *const *rlast,
+                                   const int *locked, const int *step, const float *learning_rate,
+                                   float alpha, float replica_momentum, float weight_decay,
+                                   int first, unsigned flags);
 /* crossbowSynchronisationPolyakRuppert (synch/polyakruppert.c:319 -> :5-138
  * on one device, :140-317 on several) -> cbx_pr_plan_step.  The average is
  * over p = nreplicas = modelmanager->size (:15): every replica of every
