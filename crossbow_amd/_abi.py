@@ -117,6 +117,7 @@ SIGNATURES = {
     "cbx_step_and_synchronise_clipped": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
     "cbx_step_and_synchronise_clipped_variables": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
     "cbx_step_and_synchronise_elastic": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
+    "cbx_step_and_synchronise_ssgd": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
     "cbx_unlock_any": (_I, [_P]),
     "cbx_checkpoint_model": (_I, [_P, _CP]),
     "cbx_override_model_data": (_I, [_P, _CP]),
@@ -214,6 +215,8 @@ SIGNATURES = {
     "cbx_sma_plan_gradient_norm": (_I, [_P, _I, _I, _P, _P, _F, _I, _I, _FP, _FP]),
     "cbx_sma_plan_average_batchnorm": (_I, [_P, _I, _IP, _PP, _PP, _IP]),
     "cbx_ssgd_plan_step": (_I, [_P, _PP, _PP, _PP, _PP, _I, _IP, _PP, _IP, _F, _I, _I]),
+    "cbx_ssgd_plan_step_and_optimise": (_I, [_P, _PP, _PP, _PP, _PP, _I, _IP, _PP, _PP, _IP, _IP, _FP, _F, _F, _I, _I,
+                                             _c.c_uint]),
     "cbx_ssgd_accumulate_buffers": (_I, [_P, _P, _P, _P, _c.c_longlong, _F, _F]),
     "cbx_ea_plan_step": (_I, [_P, _PP, _PP, _I, _IP, _PP, _PP, _IP, _F, _I]),
     "cbx_ea_plan_step_and_optimise": (_I, [_P, _PP, _PP, _I, _IP, _PP, _PP, _PP, _PP, _IP, _IP, _FP, _F, _F, _F, _I,

@@ -16,6 +16,7 @@
 //   * errors return codes; the JNI shim turns them back into exit(1).
 #include "context_internal.h"
 #include "optimise_plan.h"
+#include "task_ssgd_internal.h"
 
 using namespace cbx::host;
 
@@ -707,7 +708,8 @@ enum FusedMode { FusedPlain, FusedVariables, FusedClipped, FusedClippedVariables
 
 // What every fused call checks first, of its arguments and of the devices: the
 // same refusals in the same order for the SMA calls and the elastic one (`me`).
-static int check_fused_call(cbx_context *c, const char *me, int first, const int *tasks, unsigned flags) {
+static int check_fused_call(cbx_context *c, const char *me, int first, const int *tasks, unsigned flags,
+                            const char *instead = nullptr) {
   TRY(check_manager_q(c));
   if (first < 0 || first > c->size) return fail(CBX_ERR_INVALID, "first replica %d out of range", first);
   if (!tasks) return fail(CBX_ERR_INVALID, "%s: null task list (one entry per replica: a task number, or -1)", me);
@@ -722,11 +724,14 @@ static int check_fused_call(cbx_context *c, const char *me, int first, const int
     if (!c->locked[id]) return fail(CBX_ERR_INVALID, "%s: stepping replica %d is not locked for this barrier", me, id);
     if (id < first) return fail(CBX_ERR_INVALID, "%s: stepping replica %d is below the first replica %d", me, id, first);
   }
+  // `instead` (the synchronous-SGD call): the refusal also names the calls to take
   if (c->G > 1 || c->devs.size() != 1)
     return fail(CBX_ERR_UNSUPPORTED, "%s: %d devices; the task steps are fused into the one-GPU barrier only, not into "
-                "kernel A of the split path", me, c->G > 1 ? c->G : (int)c->devs.size());
+                "kernel A of the split path%s%s", me, c->G > 1 ? c->G : (int)c->devs.size(), instead ? "; use " : "",
+                instead ? instead : "");
   if (c->force_split)
-    return fail(CBX_ERR_UNSUPPORTED, "%s: cbx_set_force_split is on; kernel A of the split path is not fused", me);
+    return fail(CBX_ERR_UNSUPPORTED, "%s: cbx_set_force_split is on; kernel A of the split path is not fused%s%s", me,
+                instead ? "; use " : "", instead ? instead : "");
   return CBX_OK;
 }
 
@@ -985,6 +990,111 @@ int cbx_step_and_synchronise_elastic(cbx_context *c, int first, int clock, int a
   const bool keep = (flags & CBX_STEP_DISCARD_TASK_OUTPUTS) == 0;
   HIP_TRY(cbx::launch_task_elastic(a, keep, cfg, d.stream, {step_start_event(c, d, 0), step_stop_event(c, d, EV_A)}));
   close_fused_step(c, d);  // the ring slot, cross_valid = false: averaging_step's fused form
+  TRY(finish_step(c));
+  return finish_barrier(c, clock, autotune);
+}
+
+// The pending task steps of the locked replicas and the one-GPU synchronous-SGD
+// barrier in one launch (task_ssgd_kernels.hip): for update model WORKER, whose
+// task steps move the device's base gradient on the sync stream
+// (ssgd_worker_step) and whose barrier broadcasts the base model (ssgd_step).
+// The stepping replicas, in ascending id order as the sequence enqueues them,
+// and the receiving ones are two lists.  The same validation before the first
+// side effect; replica momentum, per-variable multipliers, s and copy flags play
+// no part, as in the two calls.  It ends as ssgd_step's unsplit form does.
+int cbx_step_and_synchronise_ssgd(cbx_context *c, int first, int clock, int autotune, const int *tasks,
+                                  void *const *streams, unsigned flags) {
+  const char *me = "cbx_step_and_synchronise_ssgd";
+  const char *instead = "cbx_replica_optimise and cbx_synchronise";
+  TraceRange trace(me);
+  TRY(check_fused_call(c, me, first, tasks, flags, instead));
+  const int size = c->size;
+  const int type = c->model.type;
+  if (type != CBX_UPDATE_WORKER)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: update model %d; only WORKER (1) is fused here; %s", me, type,
+                type == CBX_UPDATE_SYNCHRONOUSEAMSGD && c->elastic_average
+                    ? "elastic averaging takes cbx_step_and_synchronise_elastic"
+                : type == CBX_UPDATE_SMA || type == CBX_UPDATE_SYNCHRONOUSEAMSGD
+                    ? "the SMA barrier takes cbx_step_and_synchronise"
+                    : "use cbx_replica_optimise and cbx_synchronise");
+  if (c->clip_on())
+    return fail(CBX_ERR_UNSUPPORTED, "%s: gradient clipping is on, and update model WORKER has no clipped step; turn it "
+                "off (cbx_set_gradient_clip) and use %s", me, instead);
+  Device &d = c->devs[0];
+  const SolverConf *ref = nullptr;  // the first stepping replica's configuration (null: nobody steps)
+  int participating = 0;
+  for (int id : d.replicas) {
+    if (id < first || !c->locked[id]) continue;
+    ++participating;
+    if (tasks[id] < 0) continue;
+    const SolverConf &conf = c->replicas[id]->conf;
+    if (conf.momentumMethod == 1)  // synchronoussgd.cu:42-44, whatever the momentum
+      return fail(CBX_ERR_UNSUPPORTED, "%s: replica %d: Nesterov's momentum has been disabled; %s refuses it too", me, id,
+                  "cbx_replica_optimise");
+    if (!ref) ref = &conf;
+    if (conf.weightDecay != ref->weightDecay)
+      return fail(CBX_ERR_UNSUPPORTED, "%s: replica %d steps with weight decay %g, an earlier one with %g; one launch "
+                  "takes one; use %s", me, id, (double)conf.weightDecay, (double)ref->weightDecay, instead);
+  }
+  if (participating > cbx::kMaxReplicas)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: more than %d locked replicas on one device; use %s", me, cbx::kMaxReplicas,
+                instead);
+  if (c->model.wpc <= 0) return fail(CBX_ERR_STATE, "S-SGD needs the work per clock (setModelWorkPerClock)");
+  // what conf.learning_rate would refuse, before any replica's query has raised a flag
+  for (int id = 0; id < size; ++id) {
+    if (tasks[id] < 0) continue;
+    const SolverConf &conf = c->replicas[id]->conf;
+    if (conf.policy == LR_STEP && conf.size <= 0) return fail(CBX_ERR_STATE, "step learning-rate policy with size 0");
+    if (conf.policy == LR_LSR && conf.warmuptasks <= 0) return fail(CBX_ERR_STATE, "LSR policy without warm-up tasks");
+    if (conf.policy == LR_CLR) return fail(CBX_ERR_UNSUPPORTED, "circular learning rate is unsupported");
+    if (conf.policy < LR_FIXED || conf.policy > LR_LSR)
+      return fail(CBX_ERR_UNSUPPORTED, "learning-rate policy %d unsupported", (int)conf.policy);
+  }
+
+  // The rates, in id order: a query may raise the replica's `_copy`
+  // (solverconfiguration.c:133,147), which this barrier leaves as it finds it.
+  std::vector<float> lr((size_t)size, 0.0f);
+  for (int id = 0; id < size; ++id)
+    if (tasks[id] >= 0) TRY(c->replicas[id]->conf.learning_rate(tasks[id], &lr[(size_t)id]));
+
+  cbx::TaskSsgdArgs a;
+  std::memset(&a, 0, sizeof(a));
+  std::vector<hipStream_t> callers;
+  for (int id : d.replicas) {  // increasing id order: the sequence's enqueue order, and common.c:208
+    if (id < first || !c->locked[id]) continue;
+    Replica &r = *c->replicas[id];
+    a.w[a.nrecv++] = reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_DATA));
+    if (tasks[id] < 0) continue;
+    const int k = a.nstep++;
+    a.sw[k] = reinterpret_cast<const cbx::v4f *>(replica_dev(d, r, CBX_BUF_DATA));
+    a.g[k] = reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_GRADIENT));
+    a.rate[k] = -lr[(size_t)id];  // synchronoussgd.cu:46
+    hipStream_t st = streams && streams[id] ? reinterpret_cast<hipStream_t>(streams[id]) : d.stream;
+    if (st != d.stream && std::find(callers.begin(), callers.end(), st) == callers.end()) callers.push_back(st);
+  }
+  const bool mom = c->has_last && c->model.conf.momentum > 0;  // synchronoussgd.c:64 (base conf)
+  a.z = reinterpret_cast<cbx::v4f *>(base_dev(c, d, CBX_BUF_DATA));
+  a.last = mom ? reinterpret_cast<cbx::v4f *>(base_dev(c, d, CBX_BUF_LAST)) : nullptr;
+  a.acc = reinterpret_cast<cbx::v4f *>(base_dev(c, d, CBX_BUF_GRADIENT));
+  a.n4 = c->n4;
+  a.wd = ref && ref->weightDecay > 0 ? ref->weightDecay : 0.0f;
+  a.ratio = (float)(1.0 / (double)(float)c->model.wpc);  // synchronoussgd.c:55
+  a.momentum = mom ? c->model.conf.momentum : 0.0f;
+
+  // The launch comes after the gradients (synchronoussgd.cu:38-40): one deferred
+  // wait per caller stream, queued now, as cbx_synchronise queues the task steps'.
+  HIP_TRY(hipSetDevice(d.hip_id));
+  if (!c->fault_skip_task_wait)
+    for (hipStream_t st : callers) TRY(defer_task_wait(d, st));
+  TRY(flush_task_waits(c));
+  // as cbx_synchronise counts a barrier that is not SMA's: its start is a marker of its own (step_start_event)
+  c->foreign_ops.fetch_add(1, std::memory_order_relaxed);
+
+  cbx::LaunchConfig cfg = c->task_barrier_cfg;
+  cfg.num_cus = d.num_cus;
+  const bool keep = (flags & CBX_STEP_DISCARD_TASK_OUTPUTS) == 0;
+  HIP_TRY(cbx::launch_task_ssgd(a, keep, cfg, d.stream, {step_start_event(c, d, 0), step_stop_event(c, d, EV_A)}));
+  close_fused_step(c, d);  // the ring slot, cross_valid = false, last_step_split = false: ssgd_step's unsplit form
   TRY(finish_step(c));
   return finish_barrier(c, clock, autotune);
 }

@@ -33,6 +33,7 @@
 // which they are enqueued, its diagrams, and the bucket geometry.
 #include "context_internal.h"
 #include "optimise_plan.h"
+#include "task_ssgd_internal.h"
 
 using namespace cbx::host;
 
@@ -816,6 +817,81 @@ int cbx_ssgd_plan_step(cbx_sma_plan *p, void *const *streams, float *const *z, f
   for (int k = 0; k < G; ++k)
     lanes.push_back({PlanLane(p, k, streams, acc[k], false), args[k]});
   return reduce_apply(lanes, grid, p->ranks > 1, group_begin, group_end);
+}
+
+// The task steps of kernels/optimisers/synchronoussgd.cu of every stepping
+// replica, in id order, and the one-device synchronous-SGD barrier
+// (synch/synchronoussgd.c:13-106, common.c:198-220) in one launch over the
+// caller's buffers: the context's cbx_step_and_synchronise_ssgd (context.hip)
+// with the caller's rates and stream order.  cbx_ssgd_plan_step plus g, step,
+// learning_rate, weight_decay and flags.  The bulk runs the context's float4
+// loop, the elements past it the kernel's TAIL workgroups
+// (task_ssgd_kernels.hip).  Everything is validated before the launch; the plan
+// queues no wait of its own.
+int cbx_ssgd_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *const *z, float *const *last,
+                                    float *const *acc, int nreplicas, const int *replica_device, float *const *w,
+                                    float *const *g, const int *locked, const int *step, const float *learning_rate,
+                                    float momentum, float weight_decay, int wpc, int first, unsigned flags) {
+  const char *me = "cbx_ssgd_plan_step_and_optimise";
+  TraceRange trace(me);
+  if (!p) return fail(CBX_ERR_INVALID, "null plan");
+  if (!streams || !z || !acc || nreplicas < 0 || (nreplicas > 0 && (!replica_device || !w || !locked || !step)))
+    return fail(CBX_ERR_INVALID, "%s: missing arguments", me);
+  if (flags & ~CBX_STEP_DISCARD_TASK_OUTPUTS) return fail(CBX_ERR_INVALID, "%s: unknown flag bits 0x%x", me, flags);
+  if (wpc <= 0) return fail(CBX_ERR_INVALID, "%s: S-SGD needs the work per clock (wpc %d)", me, wpc);
+  if (first < 0 || first > nreplicas) return fail(CBX_ERR_INVALID, "%s: first replica %d out of range", me, first);
+  const bool keep = (flags & CBX_STEP_DISCARD_TASK_OUTPUTS) == 0;
+  const bool mom = momentum > 0.0f;     // synchronoussgd.c:64
+  const bool wd = weight_decay > 0.0f;  // synchronoussgd.cu:20
+  if (mom && !last) return fail(CBX_ERR_INVALID, "%s: momentum > 0 needs the base model's last buffer", me);
+  for (int id = 0; id < nreplicas; ++id) {
+    if (!step[id]) continue;
+    if (!locked[id]) return fail(CBX_ERR_INVALID, "%s: stepping replica %d is not locked for this barrier", me, id);
+    if (id < first) return fail(CBX_ERR_INVALID, "%s: stepping replica %d is below the first replica %d", me, id, first);
+    if (!g || !learning_rate) return fail(CBX_ERR_INVALID, "%s: a stepping replica needs g and learning_rate", me);
+  }
+  if (p->devs.size() != 1 || p->ranks != 1)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: a plan of %d devices and %d ranks; the task steps are fused into the one-GPU "
+                "barrier only; use cbx_ssgd_accumulate_buffers and cbx_ssgd_plan_step", me, (int)p->devs.size(), p->ranks);
+  if (!z[0] || !acc[0] || !aligned16(z[0]) || !aligned16(acc[0]) || (mom && (!last[0] || !aligned16(last[0]))))
+    return fail(CBX_ERR_INVALID, "%s: base buffers must be non-null and 16-byte aligned", me);
+  cbx::TaskSsgdArgs a;
+  std::memset(&a, 0, sizeof(a));
+  int participating = 0;
+  for (int id = first; id < nreplicas; ++id) {  // increasing id order: the steps' enqueue order, and common.c:208
+    if (!locked[id]) continue;
+    if (replica_device[id] != 0) return fail(CBX_ERR_INVALID, "%s: replica %d on device %d of 1", me, id, replica_device[id]);
+    const bool st = step[id] != 0;
+    if (!w[id] || !aligned16(w[id])) return fail(CBX_ERR_INVALID, "%s: replica %d: w must be non-null and 16-byte aligned", me, id);
+    // a replica that only joins is one write stream: its g may be NULL
+    if (st && (!g[id] || !aligned16(g[id])))
+      return fail(CBX_ERR_INVALID, "%s: stepping replica %d: g must be non-null and 16-byte aligned", me, id);
+    if (++participating > cbx::kMaxReplicas) continue;  // counted on, refused below
+    a.w[a.nrecv++] = reinterpret_cast<cbx::v4f *>(w[id]);
+    if (!st) continue;
+    const int k = a.nstep++;
+    a.sw[k] = reinterpret_cast<const cbx::v4f *>(w[id]);
+    a.g[k] = reinterpret_cast<cbx::v4f *>(g[id]);
+    a.rate[k] = -1.0f * learning_rate[id];  // synchronoussgd.cu:46
+  }
+  if (participating > cbx::kMaxReplicas)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: %d participating replicas, more than %d on one device", me, participating,
+                cbx::kMaxReplicas);
+  a.z = reinterpret_cast<cbx::v4f *>(z[0]);
+  a.last = mom ? reinterpret_cast<cbx::v4f *>(last[0]) : nullptr;
+  a.acc = reinterpret_cast<cbx::v4f *>(acc[0]);
+  a.n4 = p->n4b;
+  a.wd = a.nstep > 0 && wd ? weight_decay : 0.0f;
+  a.ratio = (float)(1.0 / (double)(float)wpc);  // synchronoussgd.c:55
+  a.momentum = mom ? momentum : 0.0f;
+  a.tail_lo = p->n4b * 4;  // the elements past the last whole chunk ride the same launch
+  a.tail_hi = p->n;
+  auto &d = p->devs[0];
+  HIP_TRY(hipSetDevice(d.hip_id));
+  cbx::LaunchConfig cfg = p->task_barrier_cfg;
+  cfg.num_cus = d.num_cus;
+  HIP_TRY(cbx::launch_task_ssgd(a, keep, cfg, static_cast<hipStream_t>(streams[0]), p->next_timing()));
+  return CBX_OK;
 }
 
 // crossbowKernelOptimiserSynchronousSGD (kernels/optimisers/synchronoussgd.cu:

@@ -153,6 +153,24 @@ class SmaPlan:
             len(replicas), _ints([r[0] for r in replicas]), _ptrs([r[1] for r in replicas]),
             _ints([r[2] for r in replicas]), ctypes.c_float(momentum), wpc, first), "cbx_ssgd_plan_step")
 
+    def ssgd_step_and_optimise(self, streams: Sequence[int], z: Sequence[int], last: Optional[Sequence[Optional[int]]],
+                               acc: Sequence[int], replicas: Sequence[Tuple[int, int, Optional[int], int, int, float]],
+                               momentum: float, weight_decay: float, wpc: int, first: int = 0,
+                               flags: int = 0) -> None:
+        """The stepping replicas' task steps and the synchronous-SGD barrier in
+        one launch (``cbx_ssgd_plan_step_and_optimise``; one device, one rank).
+        ``replicas[id]`` = (device index, w, g, locked, step, learning_rate);
+        ``g`` may be None for a replica that only joins.  ``last`` may be None
+        when ``momentum`` is 0.  The caller orders ``streams[0]`` behind the
+        gradients."""
+        rate = (ctypes.c_float * max(1, len(replicas)))(*[float(r[5]) for r in replicas])
+        _raise(self.lib, self.lib.cbx_ssgd_plan_step_and_optimise(
+            self._p, _ptrs(streams), _ptrs(z), _ptrs(last) if last is not None else None, _ptrs(acc),
+            len(replicas), _ints([r[0] for r in replicas]), _ptrs([r[1] for r in replicas]),
+            _ptrs([r[2] for r in replicas]), _ints([r[3] for r in replicas]), _ints([r[4] for r in replicas]), rate,
+            ctypes.c_float(momentum), ctypes.c_float(weight_decay), wpc, first, ctypes.c_uint(flags)),
+            "cbx_ssgd_plan_step_and_optimise")
+
     def elastic_step(self, streams: Sequence[int], z: Sequence[int],
                      replicas: Sequence[Tuple[int, int, Optional[int], int]], alpha: float, first: int = 0) -> None:
         """One elastic-averaging barrier (``cbx_ea_plan_step``).  ``replicas[id]``

@@ -253,6 +253,17 @@ class TheGPU:
         return self._step_and_synchronise(self._L.cbx_step_and_synchronise_elastic, first, clock, autotune, tasks,
                                           streams, flags)
 
+    def step_and_synchronise_ssgd(self, first: int, clock: int, autotune: int, tasks: Sequence[int],
+                                  streams: Optional[Sequence[Optional[int]]] = None, flags: int = 0) -> int:
+        """``cbx_step_and_synchronise_ssgd``: ``step_and_synchronise`` for
+        synchronous SGD (update model WORKER), which that call refuses: the
+        pending task steps, in ascending id order, and the one-GPU S-SGD
+        barrier in one launch.  Same arguments; the base gradient is read as
+        the call finds it and left zero, every participating replica becomes
+        the new base model."""
+        return self._step_and_synchronise(self._L.cbx_step_and_synchronise_ssgd, first, clock, autotune, tasks,
+                                          streams, flags)
+
     def _step_and_synchronise(self, fn, first, clock, autotune, tasks, streams, flags) -> int:
         tasks = list(tasks)
         N = self.num_replicas()

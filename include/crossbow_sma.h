@@ -409,6 +409,64 @@ int cbx_step_and_synchronise_clipped_variables (cbx_context *ctx, int first, int
  * The launch shape is cbx_set_task_barrier_kernel_config's.                 */
 int cbx_step_and_synchronise_elastic (cbx_context *ctx, int first, int clock, int autotune,
                                       const int *tasks, void *const *streams, unsigned flags);
+/* The pending task steps of the locked replicas and the one-GPU
+ * synchronous-SGD barrier in one launch: cbx_step_and_synchronise for update
+ * model WORKER (1; kernels/optimisers/synchronoussgd.cu:3-56 and
+ * synch/synchronoussgd.c:13-106 with common.c:198-220), which the calls above
+ * refuse.  Same parameters: tasks[id] is replica id's task number, or -1 when it
+ * only joins the barrier; streams[id] the stream its gradient was produced on
+ * (NULL: the sync stream), behind which the launch is ordered.  Asynchronous.
+ *
+ * The arithmetic.  Per element, one fp32 operation per reference call:
+ *   acc = the device's base gradient as the call finds it (not assumed zero)
+ *   per stepping replica i (tasks[id] >= 0) in ASCENDING ID ORDER,
+ *   rate_i = -learning_rate (conf_i, tasks[id]):
+ *     gv = g_i
+ *     gv = fma (wd, w_i, gv); g_i = gv              (wd > 0; g_i written with outputs kept)
+ *     acc = fma (rate_i, gv, acc)
+ *   D = ratio * acc, a plain multiply, ratio = (float) (1.0 / (double) (float) wpc)
+ *   D = fma (mu, last, D); last = D                 (base momentum mu > 0: the model's, not 0.9)
+ *   z = fma (1, D, z)
+ *   base gradient = +0
+ *   w_i = z for every participating replica (locked, id >= first), stepping or
+ *   only joining.
+ * The accumulator depends on the order of its additions: the sequence below adds
+ * in enqueue order, so it is the sequence in ascending id order that this call
+ * equals.  w_i of a stepping replica is read only when wd > 0, before it is
+ * overwritten; a replica that only joins is one written buffer, its g, s and
+ * last are not read.  Replica momentum, s, the per-variable multipliers
+ * (cbx_set_variable_learning_rates) and the copy flags play no part, as in
+ * cbx_replica_optimise and cbx_synchronise under WORKER; a learning-rate query
+ * of this call that raises a replica's copy flag (MULTISTEP at its boundary)
+ * leaves it raised, as the sequence does.
+ *
+ * The contract.  With flags == 0 the call leaves every buffer (z, the base
+ * `last` and gradient, every w_i, g_i, s_i and last_i) bit for bit, and every
+ * piece of host state (copy flags, clocks, `updates`, the step event, one
+ * timing-history entry), as if the caller had made, on one device,
+ *   cbx_replica_optimise (ctx, id, tasks[id], streams[id])  for every id with
+ *                                       tasks[id] >= 0, in ascending id order,
+ *   cbx_synchronise (ctx, first, clock, autotune, 0).
+ * With CBX_STEP_DISCARD_TASK_OUTPUTS, g_i of the stepping replicas is not
+ * written; that differs from the sequence only when wd > 0 (without weight
+ * decay the step writes no g_i and the flag selects the same kernel).  The
+ * promise that goes with the flag is cbx_step_and_synchronise's: nobody reads
+ * g_i before the replica's next gradient overwrites it.  When nobody steps the
+ * call is cbx_synchronise under WORKER.
+ *
+ * Everything is checked before the first side effect: a refused call changes
+ * no buffer, flag or clock, and cbx_last_error names the cause and the calls to
+ * take instead.  CBX_ERR_INVALID: as cbx_step_and_synchronise, and first.
+ * CBX_ERR_UNSUPPORTED: more than one device, or cbx_set_force_split on; an
+ * update model other than WORKER; gradient clipping on; Nesterov momentum
+ * (momentumMethod 1) on a stepping replica; stepping replicas whose weight
+ * decay differs; more than 64 participating replicas; a learning-rate policy
+ * the library does not have.  CBX_ERR_STATE: no work per clock (wpc <= 0); a
+ * STEP policy with size 0 or an LSR policy without warm-up tasks, refused
+ * before any replica's query has raised a flag.
+ * The launch shape is cbx_set_task_barrier_kernel_config's.                 */
+int cbx_step_and_synchronise_ssgd (cbx_context *ctx, int first, int clock, int autotune,
+                                   const int *tasks, void *const *streams, unsigned flags);
 /* TheGPU.unlockAny() GPU.c:1142-1149 -> modelmanager.c:233-245           */
 int cbx_unlock_any (cbx_context *ctx);
 
@@ -1271,6 +1329,45 @@ int cbx_ssgd_plan_step (cbx_sma_plan *plan, void *const *streams, float *const *
                         const int *locked, float momentum, int wpc, int first);
 int cbx_ssgd_accumulate_buffers (void *stream, const float *w, float *g, float *acc, long long elements,
                                  float learning_rate, float weight_decay);
+/* The stepping replicas' task steps (kernels/optimisers/synchronoussgd.cu:3-56)
+ * and the one-device synchronous-SGD barrier (synch/synchronoussgd.c:13-106,
+ * common.c:198-220) in one launch over the caller's buffers of exactly
+ * `elements` floats: what cbx_step_and_synchronise_ssgd is to a context, for a
+ * tau = 1 S-SGD build.  With R replicas and base momentum it moves
+ * (8R + 24) n bytes where the calls move (16R + 24) n; with weight decay
+ * (16R + 24) n, or (12R + 24) n with the discard flag, against (24R + 24) n.
+ * It is cbx_ssgd_plan_step plus g, step, learning_rate, weight_decay and flags:
+ * arguments named as there, or as for cbx_sma_plan_step_and_optimise, mean the
+ * same.  g[id] may be NULL for a replica that only joins (step[id] == 0: it is
+ * one written buffer); `g` and `learning_rate` themselves may be NULL when
+ * nobody steps; `last` may be NULL, and is not used, when momentum == 0.  The
+ * arithmetic is cbx_step_and_synchronise_ssgd's, the stepping replicas in
+ * ascending id order, the accumulator starting from what acc[0] holds.
+ * The contract.  With flags == 0 every buffer (z, last, acc, every w and g) is
+ * left bit for bit as after
+ *   cbx_ssgd_accumulate_buffers (streams[0], w[id], g[id], acc[0], elements,
+ *       learning_rate[id], weight_decay)
+ *                                 for every id with step[id] != 0, in id order,
+ *   cbx_ssgd_plan_step (plan, streams, z, last, acc, nreplicas, replica_device,
+ *       w, locked, momentum, wpc, first)   on a one-device, one-rank plan.
+ * With CBX_STEP_DISCARD_TASK_OUTPUTS, g[id] of the stepping replicas is not
+ * written (a difference only when weight_decay > 0).  Nothing at or past
+ * `elements` is read or written: the last elements ride the same launch on
+ * extra workgroups in front.  One launch on streams[0], asynchronous; the caller
+ * orders streams[0] behind the gradients.  With cbx_sma_plan_set_timing on, the
+ * launch stamps itself into the plan's ring.
+ * Everything is checked before the launch, as in cbx_ea_plan_step_and_optimise:
+ * CBX_ERR_INVALID for a missing argument, an unknown flag bit, wpc <= 0, `first`
+ * out of range, a stepping replica that is not locked or below `first`, a
+ * participating replica on a device other than 0 or with a missing or
+ * misaligned buffer; CBX_ERR_UNSUPPORTED for a plan with more than one device
+ * or rank, and for more than 64 participating replicas.  Returns CBX_OK or an
+ * error.                                                                   */
+int cbx_ssgd_plan_step_and_optimise (cbx_sma_plan *plan, void *const *streams, float *const *z, float *const *last,
+                                     float *const *acc, int nreplicas, const int *replica_device,
+                                     float *const *w, float *const *g, const int *locked, const int *step,
+                                     const float *learning_rate, float momentum, float weight_decay,
+                                     int wpc, int first, unsigned flags);
 /* The same seam for the two averaging barriers, over an existing plan: they
  * share its acc / D scratch, communicators, comm stream, per-bucket events
  * and cbx_sma_plan_set_buckets with the SMA and S-SGD steps, so any sequence
