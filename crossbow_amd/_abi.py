@@ -117,6 +117,7 @@ SIGNATURES = {
     "cbx_step_and_synchronise_clipped": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
     "cbx_step_and_synchronise_clipped_variables": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
     "cbx_step_and_synchronise_elastic": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
+    "cbx_step_and_synchronise_elastic_clipped_variables": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
     "cbx_step_and_synchronise_ssgd": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
     "cbx_unlock_any": (_I, [_P]),
     "cbx_checkpoint_model": (_I, [_P, _CP]),
@@ -221,6 +222,8 @@ SIGNATURES = {
     "cbx_ea_plan_step": (_I, [_P, _PP, _PP, _I, _IP, _PP, _PP, _IP, _F, _I]),
     "cbx_ea_plan_step_and_optimise": (_I, [_P, _PP, _PP, _I, _IP, _PP, _PP, _PP, _PP, _IP, _IP, _FP, _F, _F, _F, _I,
                                            _c.c_uint]),
+    "cbx_ea_plan_step_and_optimise_clipped_variables": (_I, [_P, _PP, _PP, _I, _IP, _PP, _PP, _PP, _PP, _IP, _IP, _FP,
+                                                             _IP, _F, _I, _I, _F, _F, _F, _I, _c.c_uint]),
     "cbx_pr_plan_step": (_I, [_P, _PP, _PP, _PP, _I, _IP, _PP, _IP, _IP, _F, _I, _I]),
 }
 

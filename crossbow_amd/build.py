@@ -18,6 +18,12 @@
   the elastic-averaging barrier (csrc/task_elastic_kernels.hip): likewise.
 * ``crossbow_amd/libcrossbow_sma_ssgd_steps.so`` -- the task steps fused into
   the synchronous-SGD barrier (csrc/task_ssgd_kernels.hip): likewise.
+* ``crossbow_amd/libcrossbow_sma_elastic_policies.so`` -- the per-variable, the
+  clipped and the clipped per-variable task steps fused into the
+  elastic-averaging barrier (csrc/task_elastic_variables_kernels.hip,
+  csrc/task_elastic_clipped_kernels.hip,
+  csrc/task_elastic_clipped_variables_kernels.hip, one compilation unit per
+  policy): likewise.
 * ``crossbow_amd/libGPU.so``           -- the JNI shim exporting Crossbow's
   ``TheGPU`` model-path natives; built only where ``jni.h`` exists (there is
   no JDK in this image).
@@ -41,6 +47,7 @@ CLIPPED_LIB = os.path.join(PKG, "libcrossbow_sma_clipped.so")
 CLIPPED_VARIABLES_LIB = os.path.join(PKG, "libcrossbow_sma_clipped_variables.so")
 ELASTIC_STEPS_LIB = os.path.join(PKG, "libcrossbow_sma_elastic_steps.so")
 SSGD_STEPS_LIB = os.path.join(PKG, "libcrossbow_sma_ssgd_steps.so")
+ELASTIC_POLICIES_LIB = os.path.join(PKG, "libcrossbow_sma_elastic_policies.so")
 JNI_LIB = os.path.join(PKG, "libGPU.so")
 ARCH = "gfx950"
 
@@ -59,10 +66,14 @@ CLIPPED_SOURCES = ("task_barrier_clipped_kernels.hip",)
 CLIPPED_VARIABLES_SOURCES = ("task_barrier_clipped_variables_kernels.hip",)
 ELASTIC_STEPS_SOURCES = ("task_elastic_kernels.hip",)
 SSGD_STEPS_SOURCES = ("task_ssgd_kernels.hip",)
+ELASTIC_POLICIES_SOURCES = ("task_elastic_clipped_variables_kernels.hip", "task_elastic_clipped_kernels.hip",
+                            "task_elastic_variables_kernels.hip")
 HEADERS = ("context_internal.h", "sma_internal.h", "stream_helpers.h", "stats_internal.h", "stats_plan.h",
            "optimise_plan.h", "clip_internal.h", "bucket_pipeline.h", "task_ssgd_internal.h",
            # the fused task-step barrier's four kernel files are one text
-           "task_barrier_step.h", "task_barrier_body.inc", "task_barrier_launch.h")
+           "task_barrier_step.h", "task_barrier_body.inc", "task_barrier_launch.h",
+           # and so are the three policy kernels of the fused elastic-averaging barrier
+           "task_elastic_policy.h", "task_elastic_policy_body.inc")
 
 
 def _sources(names=SOURCES):
@@ -72,6 +83,7 @@ def _sources(names=SOURCES):
 def _deps():
     return (_sources() + _sources(VARIABLES_SOURCES) + _sources(CLIPPED_SOURCES) +
             _sources(CLIPPED_VARIABLES_SOURCES) + _sources(ELASTIC_STEPS_SOURCES) + _sources(SSGD_STEPS_SOURCES) +
+            _sources(ELASTIC_POLICIES_SOURCES) +
             [os.path.join(CSRC, f) for f in HEADERS] + [os.path.join(ROOT, "include", "crossbow_sma.h"),
                                                         os.path.abspath(__file__)])
 
@@ -128,29 +140,30 @@ def _link(target, objs, libs, verbose):
 
 
 def build_lib(force: bool = False, verbose: bool = False) -> str:
-    # one staleness check for all six libraries: they share the headers
+    # one staleness check for all seven libraries: they share the headers
     if not force and not any(_stale(t, _deps()) for t in (LIB, VARIABLES_LIB, CLIPPED_LIB, CLIPPED_VARIABLES_LIB,
-                                                          ELASTIC_STEPS_LIB, SSGD_STEPS_LIB)):
+                                                          ELASTIC_STEPS_LIB, SSGD_STEPS_LIB, ELASTIC_POLICIES_LIB)):
         return LIB
     objdir = os.path.join(PKG, "build")
     os.makedirs(objdir, exist_ok=True)
-    # every source of the six objects is compiled in one pool, the slowest (the barrier kernels) first
+    # every source of the seven objects is compiled in one pool, the slowest (the barrier kernels) first
     groups = (VARIABLES_SOURCES, CLIPPED_SOURCES, CLIPPED_VARIABLES_SOURCES, ELASTIC_STEPS_SOURCES, SSGD_STEPS_SOURCES,
-              tuple(reversed(SOURCES)))
+              ELASTIC_POLICIES_SOURCES, tuple(reversed(SOURCES)))
     objs = _compile([src for names in groups for src in _sources(names)], objdir, verbose)
     side = (len(VARIABLES_SOURCES), len(CLIPPED_SOURCES), len(CLIPPED_VARIABLES_SOURCES), len(ELASTIC_STEPS_SOURCES),
-            len(SSGD_STEPS_SOURCES))
-    at = [sum(side[:k]) for k in range(6)]
-    # the objects of the per-variable, the clipped and the clipped per-variable fused barrier and of the fused
-    # elastic-averaging and synchronous-SGD barriers first: the library links against them
+            len(SSGD_STEPS_SOURCES), len(ELASTIC_POLICIES_SOURCES))
+    at = [sum(side[:k]) for k in range(7)]
+    # the objects of the per-variable, the clipped and the clipped per-variable fused barrier, of the fused
+    # elastic-averaging and synchronous-SGD barriers and of the former's policies first: the library links against them
     _link(VARIABLES_LIB, objs[at[0]:at[1]], [], verbose)
     _link(CLIPPED_LIB, objs[at[1]:at[2]], [], verbose)
     _link(CLIPPED_VARIABLES_LIB, objs[at[2]:at[3]], [], verbose)
     _link(ELASTIC_STEPS_LIB, objs[at[3]:at[4]], [], verbose)
     _link(SSGD_STEPS_LIB, objs[at[4]:at[5]], [], verbose)
-    _link(LIB, list(reversed(objs[at[5]:])),
+    _link(ELASTIC_POLICIES_LIB, objs[at[5]:at[6]], [], verbose)
+    _link(LIB, list(reversed(objs[at[6]:])),
           ["-L", PKG, "-lcrossbow_sma_variables", "-lcrossbow_sma_clipped", "-lcrossbow_sma_clipped_variables",
-           "-lcrossbow_sma_elastic_steps", "-lcrossbow_sma_ssgd_steps",
+           "-lcrossbow_sma_elastic_steps", "-lcrossbow_sma_ssgd_steps", "-lcrossbow_sma_elastic_policies",
            "-Wl,-rpath,$ORIGIN", "-lrccl", "-lrocprofiler-sdk-roctx", "-lpthread"],
           verbose)
     return LIB

@@ -772,6 +772,29 @@ static int check_stepping_replicas(cbx_context *c, const char *me, int first, co
   return CBX_OK;
 }
 
+// The norm passes of a clipped fused call (the SMA barrier's and the elastic
+// one's), where cbx_replica_optimise puts them: on the replica's stream, behind
+// the last barrier's use of the replica and its record, and in front of that
+// stream's deferred wait, which then orders the launch behind them.  A pass on
+// the sync stream comes after the updates made on other streams.  S, K, the
+// scale, the flags and the counts are the sequence's bits: it is the
+// sequence's code (launch_gradient_norm).
+struct FusedNorm {
+  Replica *r;
+  hipStream_t st;
+};
+static int launch_fused_norms(cbx_context *c, Device &d, const std::vector<FusedNorm> &norms) {
+  if (norms.empty()) return CBX_OK;
+  if (std::any_of(norms.begin(), norms.end(), [&](const FusedNorm &nm) { return nm.st == d.stream; }))
+    TRY(flush_task_waits(c));
+  for (const FusedNorm &nm : norms) {
+    if (nm.st != d.stream && d.step_event) HIP_TRY(hipStreamWaitEvent(nm.st, d.step_event, 0));
+    HIP_TRY(cbx::launch_gradient_norm(replica_dev(d, *nm.r, CBX_BUF_GRADIENT), c->n, nm.r->clip, c->clip_max_norm,
+                                      c->clip_skip_nonfinite, c->clip_norm_policy, nm.st));
+  }
+  return CBX_OK;
+}
+
 static int step_and_synchronise(cbx_context *c, int first, int clock, int autotune, const int *tasks,
                                 void *const *streams, unsigned flags, FusedMode mode) {
   const bool variables = mode == FusedVariables || mode == FusedClippedVariables;
@@ -818,11 +841,7 @@ static int step_and_synchronise(cbx_context *c, int first, int clock, int autotu
   std::memset(&records, 0, sizeof(records));
   int k = 0, copies = 0;
   std::vector<hipStream_t> callers;
-  struct Norm {
-    Replica *r;
-    hipStream_t st;
-  };
-  std::vector<Norm> norms;  // the stepping replicas of a clipped call, id order
+  std::vector<FusedNorm> norms;  // the stepping replicas of a clipped call, id order
   for (int id : d.replicas) {  // increasing id order, sma.c:69
     if (id < first || !c->locked[id]) continue;
     Replica &r = *c->replicas[id];
@@ -856,21 +875,8 @@ static int step_and_synchronise(cbx_context *c, int first, int clock, int autotu
   // The launch comes after the gradients: one deferred wait per caller stream,
   // queued now, as cbx_synchronise queues the task steps' (DESIGN.md 7).
   HIP_TRY(hipSetDevice(d.hip_id));
-  // The clipped call's norm passes, where cbx_replica_optimise puts them: on
-  // the replica's stream, behind the last barrier's use of the replica and its
-  // record, and in front of that stream's deferred wait, which then orders the
-  // launch behind them.  A pass on the sync stream comes after the updates made
-  // on other streams.  S, K, the scale, the flags and the counts are the
-  // sequence's bits: it is the sequence's code (launch_gradient_norm).
-  if (!norms.empty()) {
-    if (std::any_of(norms.begin(), norms.end(), [&](const Norm &nm) { return nm.st == d.stream; }))
-      TRY(flush_task_waits(c));
-    for (const Norm &nm : norms) {
-      if (nm.st != d.stream && d.step_event) HIP_TRY(hipStreamWaitEvent(nm.st, d.step_event, 0));
-      HIP_TRY(cbx::launch_gradient_norm(replica_dev(d, *nm.r, CBX_BUF_GRADIENT), c->n, nm.r->clip, c->clip_max_norm,
-                                        c->clip_skip_nonfinite, c->clip_norm_policy, nm.st));
-    }
-  }
+  // the clipped call's norm passes, in front of the deferred waits
+  TRY(launch_fused_norms(c, d, norms));
   if (!c->fault_skip_task_wait)
     for (hipStream_t st : callers) TRY(defer_task_wait(d, st));
   TRY(flush_task_waits(c));
@@ -918,13 +924,21 @@ int cbx_step_and_synchronise_clipped_variables(cbx_context *c, int first, int cl
 // elastic-averaging barrier in one launch (task_elastic_kernels.hip): what
 // step_and_synchronise above is to the SMA barrier, for update model 3 with
 // cbx_set_elastic_average.  The same validation before the first side effect;
-// no clipped and no per-variable form, no base momentum, and no copy flag is
-// read or cleared (synchronouseamsgd.c:42-90 has no Phase D): a flag that a
-// rate query of this call raises stays raised, as after the two calls.  It ends
-// as averaging_step's fused form does.
-int cbx_step_and_synchronise_elastic(cbx_context *c, int first, int clock, int autotune, const int *tasks,
-                                     void *const *streams, unsigned flags) {
-  const char *me = "cbx_step_and_synchronise_elastic";
+// no base momentum, and no copy flag is read or cleared
+// (synchronouseamsgd.c:42-90 has no Phase D): a flag that a rate query of this
+// call raises stays raised, as after the two calls.  It ends as
+// averaging_step's fused form does.
+// cbx_step_and_synchronise_elastic (`policies` false) refuses gradient clipping
+// and per-variable rates.  cbx_step_and_synchronise_elastic_clipped_variables
+// refuses neither, as FusedClippedVariables above: with clipping on and a
+// stepping replica it runs the norm passes where the SMA call places them
+// (launch_fused_norms), and the kernel is the one of what is on
+// (libcrossbow_sma_elastic_policies.so); with both off, or clipping alone and
+// nobody stepping, it is the plain call's launch.
+static int step_and_synchronise_elastic(cbx_context *c, int first, int clock, int autotune, const int *tasks,
+                                        void *const *streams, unsigned flags, bool policies) {
+  const char *other = "cbx_step_and_synchronise_elastic_clipped_variables";
+  const char *me = policies ? other : "cbx_step_and_synchronise_elastic";
   TraceRange trace(me);
   TRY(check_fused_call(c, me, first, tasks, flags));
   const int size = c->size;
@@ -935,14 +949,21 @@ int cbx_step_and_synchronise_elastic(cbx_context *c, int first, int clock, int a
   if (type != CBX_UPDATE_SYNCHRONOUSEAMSGD)
     return fail(CBX_ERR_UNSUPPORTED, "%s: update model %d; only SYNCHRONOUSEAMSGD (3) with elastic averaging on is fused "
                 "here", me, type);
-  if (c->clip_on())
-    return fail(CBX_ERR_UNSUPPORTED, "%s: gradient clipping is on; use cbx_replica_optimise and cbx_synchronise", me);
-  if (c->variable_rates && c->model.conf.irregular > 0)
-    return fail(CBX_ERR_UNSUPPORTED, "%s: variable learning rates are on with %d irregular variables; use "
-                "cbx_replica_optimise and cbx_synchronise", me, c->model.conf.irregular);
+  const bool clip = c->clip_on();
+  const bool per_variable = c->variable_rates && c->model.conf.irregular > 0;
+  if (clip && !policies)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: gradient clipping is on; the clipped step needs its norm pass first, use %s, "
+                "or cbx_replica_optimise and cbx_synchronise", me, other);
+  if (per_variable && !policies)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: variable learning rates are on with %d irregular variables; use %s, or "
+                "cbx_replica_optimise and cbx_synchronise", me, c->model.conf.irregular, other);
+  if (per_variable && !c->var_refusal.empty())
+    return fail(CBX_ERR_UNSUPPORTED, "%s with variable learning rates: %s", me, c->var_refusal.c_str());
   Device &d = c->devs[0];
+  if (per_variable && !d.var_tables_padded.chunks)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: the padded model is too large for the chunk table", me);
   const SolverConf *ref = nullptr;  // the first stepping replica's configuration (null: nobody steps)
-  TRY(check_stepping_replicas(c, me, first, tasks, false, &ref));
+  TRY(check_stepping_replicas(c, me, first, tasks, clip, &ref));
 
   // The rates, in id order: a query may raise the replica's `_copy`
   // (solverconfiguration.c:133,147), which this barrier leaves as it finds it.
@@ -952,8 +973,11 @@ int cbx_step_and_synchronise_elastic(cbx_context *c, int first, int clock, int a
 
   cbx::TaskBarrierArgs a;
   std::memset(&a, 0, sizeof(a));
+  cbx::ClipRecordPtrs records;
+  std::memset(&records, 0, sizeof(records));
   int k = 0;
   std::vector<hipStream_t> callers;
+  std::vector<FusedNorm> norms;  // the stepping replicas of a clipped call, id order
   for (int id : d.replicas) {  // increasing id order, synchronouseamsgd.c:46
     if (id < first || !c->locked[id]) continue;
     Replica &r = *c->replicas[id];
@@ -966,6 +990,10 @@ int cbx_step_and_synchronise_elastic(cbx_context *c, int first, int clock, int a
       a.rate[k] = -lr[(size_t)id];  // sma.cu:43
       hipStream_t st = streams && streams[id] ? reinterpret_cast<hipStream_t>(streams[id]) : d.stream;
       if (st != d.stream && std::find(callers.begin(), callers.end(), st) == callers.end()) callers.push_back(st);
+      if (clip) {
+        records.p[k] = r.clip.record();
+        norms.push_back({&r, st});
+      }
     }
     ++k;
   }
@@ -979,6 +1007,8 @@ int cbx_step_and_synchronise_elastic(cbx_context *c, int first, int clock, int a
   // The launch comes after the gradients: one deferred wait per caller stream,
   // queued now, as cbx_synchronise queues the task steps' (DESIGN.md 7).
   HIP_TRY(hipSetDevice(d.hip_id));
+  // the clipped call's norm passes, in front of the deferred waits
+  TRY(launch_fused_norms(c, d, norms));
   if (!c->fault_skip_task_wait)
     for (hipStream_t st : callers) TRY(defer_task_wait(d, st));
   TRY(flush_task_waits(c));
@@ -988,10 +1018,26 @@ int cbx_step_and_synchronise_elastic(cbx_context *c, int first, int clock, int a
   cbx::LaunchConfig cfg = c->task_barrier_cfg;
   cfg.num_cus = d.num_cus;
   const bool keep = (flags & CBX_STEP_DISCARD_TASK_OUTPUTS) == 0;
-  HIP_TRY(cbx::launch_task_elastic(a, keep, cfg, d.stream, {step_start_event(c, d, 0), step_stop_event(c, d, EV_A)}));
+  const cbx::Timing tm = {step_start_event(c, d, 0), step_stop_event(c, d, EV_A)};
+  // a clipped call in which no replica steps has nothing to clip: the per-variable or the plain kernel, the same bits
+  if (per_variable && !norms.empty())
+    HIP_TRY(cbx::launch_task_elastic_clipped_variables(a, d.var_tables_padded, records, keep, cfg, d.stream, tm));
+  else if (per_variable) HIP_TRY(cbx::launch_task_elastic_variables(a, d.var_tables_padded, keep, cfg, d.stream, tm));
+  else if (!norms.empty()) HIP_TRY(cbx::launch_task_elastic_clipped(a, records, keep, cfg, d.stream, tm));
+  else HIP_TRY(cbx::launch_task_elastic(a, keep, cfg, d.stream, tm));
   close_fused_step(c, d);  // the ring slot, cross_valid = false: averaging_step's fused form
   TRY(finish_step(c));
   return finish_barrier(c, clock, autotune);
+}
+
+int cbx_step_and_synchronise_elastic(cbx_context *c, int first, int clock, int autotune, const int *tasks,
+                                     void *const *streams, unsigned flags) {
+  return step_and_synchronise_elastic(c, first, clock, autotune, tasks, streams, flags, false);
+}
+
+int cbx_step_and_synchronise_elastic_clipped_variables(cbx_context *c, int first, int clock, int autotune,
+                                                       const int *tasks, void *const *streams, unsigned flags) {
+  return step_and_synchronise_elastic(c, first, clock, autotune, tasks, streams, flags, true);
 }
 
 // The pending task steps of the locked replicas and the one-GPU synchronous-SGD

@@ -406,6 +406,26 @@ inline LaunchConfig task_barrier_launch_config() {
 // shape is launch_task_barrier's (task_barrier_launch_config).
 hipError_t launch_task_elastic(const TaskBarrierArgs &a, bool keep_task_outputs, const LaunchConfig &cfg,
                                hipStream_t stream, Timing t = {});
+// launch_task_elastic behind the three other step policies of
+// task_barrier_step.h (cbx_step_and_synchronise_elastic_clipped_variables,
+// cbx_ea_plan_step_and_optimise_clipped_variables; task_elastic_policy_body.inc
+// and the three task_elastic_*_kernels.hip, together a shared object of their
+// own: libcrossbow_sma_elastic_policies.so).  The step is that of the SMA
+// launch of the same policy (launch_task_barrier_variables,
+// launch_task_barrier_clipped, launch_task_barrier_clipped_variables), and so
+// are the arguments: `t` covers at least a.n4 * 4 floats in whole chunks and
+// a.tail_hi; rec.p[k] is the record of participating replica k, every stepping
+// replica has one, and a launch in which nobody steps is refused by the clipped
+// two.  The barrier, the compiled forms and everything else are
+// launch_task_elastic's.
+struct ClipRecordPtrs;  // clip_internal.h
+hipError_t launch_task_elastic_variables(const TaskBarrierArgs &a, const VarTables &t, bool keep_task_outputs,
+                                         const LaunchConfig &cfg, hipStream_t stream, Timing tm = {});
+hipError_t launch_task_elastic_clipped(const TaskBarrierArgs &a, const ClipRecordPtrs &rec, bool keep_task_outputs,
+                                       const LaunchConfig &cfg, hipStream_t stream, Timing tm = {});
+hipError_t launch_task_elastic_clipped_variables(const TaskBarrierArgs &a, const VarTables &t,
+                                                 const ClipRecordPtrs &rec, bool keep_task_outputs,
+                                                 const LaunchConfig &cfg, hipStream_t stream, Timing tm = {});
 // DEFAULT update model (0, kernels/optimisers/default.cu:3-131): the task
 // step moves the replica and its device's base model by the same gradient.
 // Reads w, g (, last), z; writes g (if changed), last, w, z.

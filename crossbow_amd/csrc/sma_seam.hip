@@ -702,13 +702,30 @@ int cbx_sma_plan_step_and_optimise_clipped_variables(cbx_sma_plan *p, void *cons
 // barrier has none.  The bulk runs the context's float4 loop, the elements past
 // it the kernel's TAIL workgroups (task_elastic_kernels.hip).  Everything is
 // validated before the launch; the plan queues no wait of its own.
-int cbx_ea_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *const *z, int nreplicas,
-                                  const int *replica_device, float *const *w, float *const *s, float *const *g,
-                                  float *const *rlast, const int *locked, const int *step, const float *learning_rate,
-                                  float alpha, float replica_momentum, float weight_decay, int first, unsigned flags) {
-  const char *me = "cbx_ea_plan_step_and_optimise";
+// cbx_ea_plan_step_and_optimise_clipped_variables (`policies`) is the same call
+// with two switches.  clip.slot != NULL: every stepping replica's norm pass
+// over its slot's scratch on streams[0] in front of the launch, and the clipped
+// step inside it, as SeamClipped above has them.  use_variables: the step reads
+// the plan's variable table.  The kernel is the one of what is on
+// (libcrossbow_sma_elastic_policies.so); with both off, or clipping alone and
+// nobody stepping, it is the plain call's launch.
+static int ea_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *const *z, int nreplicas,
+                                     const int *replica_device, float *const *w, float *const *s, float *const *g,
+                                     float *const *rlast, const int *locked, const int *step,
+                                     const float *learning_rate, float alpha, float replica_momentum,
+                                     float weight_decay, int first, unsigned flags, bool policies,
+                                     const SeamClip &clip = SeamClip(), int use_variables = 0) {
+  const char *me = policies ? "cbx_ea_plan_step_and_optimise_clipped_variables" : "cbx_ea_plan_step_and_optimise";
+  const bool clipped = clip.slot != nullptr, variables = use_variables == 1;
   TraceRange trace(me);
   if (!p) return fail(CBX_ERR_INVALID, "null plan");
+  if (use_variables != 0 && use_variables != 1)
+    return fail(CBX_ERR_INVALID, "%s: use_variables %d is neither 0 nor 1", me, use_variables);
+  if (variables && p->var_bounds.empty()) return fail(CBX_ERR_STATE, "%s with variables before cbx_sma_plan_set_variables", me);
+  if (clipped && (!(clip.max_norm >= 0.0f) || std::isinf(clip.max_norm)))
+    return fail(CBX_ERR_INVALID, "%s: max_norm %g is negative, NaN or infinite", me, (double)clip.max_norm);
+  if (clipped && clip.skip_nonfinite != 0 && clip.skip_nonfinite != 1)
+    return fail(CBX_ERR_INVALID, "%s: skip_nonfinite %d is neither 0 nor 1", me, clip.skip_nonfinite);
   if (!streams || !z || nreplicas < 0 || (nreplicas > 0 && (!replica_device || !w || !locked || !step)))
     return fail(CBX_ERR_INVALID, "%s: missing arguments", me);
   if (flags & ~CBX_STEP_DISCARD_TASK_OUTPUTS) return fail(CBX_ERR_INVALID, "%s: unknown flag bits 0x%x", me, flags);
@@ -731,6 +748,8 @@ int cbx_ea_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *
   std::memset(&a, 0, sizeof(a));
   int participating = 0;
   bool steps = false;
+  int slot_of[cbx::kMaxReplicas];  // clipped: the slot of participating replica k, or -1
+  uint64_t slots_taken = 0;
   for (int id = first; id < nreplicas; ++id) {  // increasing id order, synchronouseamsgd.c:46
     if (!locked[id]) continue;
     if (replica_device[id] != 0) return fail(CBX_ERR_INVALID, "%s: replica %d on device %d of 1", me, id, replica_device[id]);
@@ -743,8 +762,18 @@ int cbx_ea_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *
       return fail(CBX_ERR_INVALID, "%s: stepping replica %d: g must be non-null and 16-byte aligned", me, id);
     if (st && rmom && (!rlast[id] || !aligned16(rlast[id])))
       return fail(CBX_ERR_INVALID, "%s: stepping replica %d: replica momentum > 0 needs a 16-byte aligned last buffer", me, id);
+    if (clipped && st) {
+      const int sl = clip.slot[id];
+      if (sl < 0 || sl >= cbx_sma_plan::kClipSlots)
+        return fail(CBX_ERR_INVALID, "%s: stepping replica %d: slot %d out of range [0, %d)", me, id, sl,
+                    cbx_sma_plan::kClipSlots);
+      if ((slots_taken >> sl) & 1ull)
+        return fail(CBX_ERR_INVALID, "%s: stepping replica %d: slot %d is another stepping replica's", me, id, sl);
+      slots_taken |= 1ull << sl;
+    }
     if (++participating > cbx::kMaxReplicas) continue;  // counted on, refused below
     const int k = a.nrep++;
+    slot_of[k] = clipped && st ? clip.slot[id] : -1;
     a.w[k] = reinterpret_cast<cbx::v4f *>(w[id]);
     if (st) {
       steps = true;
@@ -769,8 +798,53 @@ int cbx_ea_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *
   HIP_TRY(hipSetDevice(d.hip_id));
   cbx::LaunchConfig cfg = p->task_barrier_cfg;
   cfg.num_cus = d.num_cus;
-  HIP_TRY(cbx::launch_task_elastic(a, keep, cfg, static_cast<hipStream_t>(streams[0]), p->next_timing()));
+  hipStream_t st0 = static_cast<hipStream_t>(streams[0]);
+  if (clipped && steps) {
+    // The norm passes in id order on the launch's stream, each over its slot's
+    // scratch (allocated on first use), as cbx_sma_plan_optimise_clipped runs
+    // them: the records are the sequence's bits.  No wait is queued.
+    cbx::ClipRecordPtrs records;
+    std::memset(&records, 0, sizeof(records));
+    cbx::ClipScratch *cs[cbx::kMaxReplicas] = {};
+    for (int k = 0; k < a.nrep; ++k)  // every scratch before the first launch: a failed allocation bumps no counter
+      if (slot_of[k] >= 0) TRY(clip_slot(p, me, 0, slot_of[k], &cs[k]));
+    for (int k = 0; k < a.nrep; ++k) {
+      if (!cs[k]) continue;
+      HIP_TRY(cbx::launch_gradient_norm(reinterpret_cast<const float *>(a.g[k]), p->n, *cs[k], clip.max_norm,
+                                        clip.skip_nonfinite == 1, p->clip_norm_policy, st0));
+      records.p[k] = cs[k]->record();
+    }
+    if (variables) HIP_TRY(cbx::launch_task_elastic_clipped_variables(a, d.var_tables, records, keep, cfg, st0, p->next_timing()));
+    else HIP_TRY(cbx::launch_task_elastic_clipped(a, records, keep, cfg, st0, p->next_timing()));
+  } else if (variables)
+    HIP_TRY(cbx::launch_task_elastic_variables(a, d.var_tables, keep, cfg, st0, p->next_timing()));
+  else
+    HIP_TRY(cbx::launch_task_elastic(a, keep, cfg, st0, p->next_timing()));
   return CBX_OK;
+}
+
+int cbx_ea_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *const *z, int nreplicas,
+                                  const int *replica_device, float *const *w, float *const *s, float *const *g,
+                                  float *const *rlast, const int *locked, const int *step, const float *learning_rate,
+                                  float alpha, float replica_momentum, float weight_decay, int first, unsigned flags) {
+  return ea_plan_step_and_optimise(p, streams, z, nreplicas, replica_device, w, s, g, rlast, locked, step,
+                                   learning_rate, alpha, replica_momentum, weight_decay, first, flags, false);
+}
+
+int cbx_ea_plan_step_and_optimise_clipped_variables(cbx_sma_plan *p, void *const *streams, float *const *z,
+                                                    int nreplicas, const int *replica_device, float *const *w,
+                                                    float *const *s, float *const *g, float *const *rlast,
+                                                    const int *locked, const int *step, const float *learning_rate,
+                                                    const int *slot, float max_norm, int skip_nonfinite,
+                                                    int use_variables, float alpha, float replica_momentum,
+                                                    float weight_decay, int first, unsigned flags) {
+  SeamClip clip;
+  clip.slot = slot;
+  clip.max_norm = max_norm;
+  clip.skip_nonfinite = skip_nonfinite;
+  return ea_plan_step_and_optimise(p, streams, z, nreplicas, replica_device, w, s, g, rlast, locked, step,
+                                   learning_rate, alpha, replica_momentum, weight_decay, first, flags, true, clip,
+                                   use_variables);
 }
 
 // crossbowSynchronisationSynchronousSGD (synch/synchronoussgd.c:13-106) over

@@ -202,6 +202,32 @@ class SmaPlan:
             ctypes.c_float(alpha), ctypes.c_float(replica_momentum), ctypes.c_float(weight_decay), first,
             ctypes.c_uint(flags)), "cbx_ea_plan_step_and_optimise")
 
+    def elastic_step_and_optimise_clipped_variables(self, streams: Sequence[int], z: Sequence[int], replicas,
+                                                    alpha: float, replica_momentum: float, weight_decay: float,
+                                                    first: int = 0, flags: int = 0,
+                                                    slots: Optional[Sequence[int]] = None, max_norm: float = 0.0,
+                                                    skip_nonfinite: bool = False,
+                                                    use_variables: bool = False) -> None:
+        """``elastic_step_and_optimise`` with the clipped step of
+        ``optimise_clipped``, a learning rate per variable, or both
+        (``cbx_ea_plan_step_and_optimise_clipped_variables``).  Clipping is on
+        iff ``slots`` is given: stepping replica id is clipped to ``max_norm``
+        (0: none) through the record of ``slots[id]``, whose norm pass the call
+        runs on ``streams[0]`` first, and skipped when ``skip_nonfinite`` and
+        its gradient holds a NaN or an infinity.  ``use_variables``: variable v
+        steps at ``learning_rate * multipliers[v]`` of the table
+        ``set_variables`` installed.  Otherwise the same arguments; with
+        neither it is ``elastic_step_and_optimise``."""
+        rate = (ctypes.c_float * max(1, len(replicas)))(*[float(r[7]) for r in replicas])
+        _raise(self.lib, self.lib.cbx_ea_plan_step_and_optimise_clipped_variables(
+            self._p, _ptrs(streams), _ptrs(z), len(replicas), _ints([r[0] for r in replicas]),
+            _ptrs([r[1] for r in replicas]), _ptrs([r[2] for r in replicas]), _ptrs([r[3] for r in replicas]),
+            _ptrs([r[4] for r in replicas]), _ints([r[5] for r in replicas]), _ints([r[6] for r in replicas]), rate,
+            _ints(slots) if slots is not None else None, ctypes.c_float(max_norm), 1 if skip_nonfinite else 0,
+            1 if use_variables else 0, ctypes.c_float(alpha), ctypes.c_float(replica_momentum),
+            ctypes.c_float(weight_decay), first, ctypes.c_uint(flags)),
+            "cbx_ea_plan_step_and_optimise_clipped_variables")
+
     def polyak_step(self, streams: Sequence[int], z: Sequence[int], last: Optional[Sequence[Optional[int]]],
                     replicas: Sequence[Tuple[int, int, int, int]], alpha: float, clock: int, first: int = 0) -> int:
         """One Polyak-Ruppert barrier (``cbx_pr_plan_step``).  ``replicas[id]`` =

@@ -253,6 +253,20 @@ class TheGPU:
         return self._step_and_synchronise(self._L.cbx_step_and_synchronise_elastic, first, clock, autotune, tasks,
                                           streams, flags)
 
+    def step_and_synchronise_elastic_clipped_variables(self, first: int, clock: int, autotune: int,
+                                                       tasks: Sequence[int],
+                                                       streams: Optional[Sequence[Optional[int]]] = None,
+                                                       flags: int = 0) -> int:
+        """``cbx_step_and_synchronise_elastic_clipped_variables``:
+        ``step_and_synchronise_elastic`` with gradient clipping on, per-variable
+        learning rates, or both, each of which that call refuses: the stepping
+        replicas' norm passes run in front of the launch, and the clipped (or
+        skipped) step at each variable's own rate inside it.  Same arguments;
+        with one of the two off the kernel is the other's, with both off it is
+        that call."""
+        return self._step_and_synchronise(self._L.cbx_step_and_synchronise_elastic_clipped_variables, first, clock,
+                                          autotune, tasks, streams, flags)
+
     def step_and_synchronise_ssgd(self, first: int, clock: int, autotune: int, tasks: Sequence[int],
                                   streams: Optional[Sequence[Optional[int]]] = None, flags: int = 0) -> int:
         """``cbx_step_and_synchronise_ssgd``: ``step_and_synchronise`` for

@@ -402,13 +402,67 @@ int cbx_step_and_synchronise_clipped_variables (cbx_context *ctx, int first, int
  * CBX_ERR_INVALID: as cbx_step_and_synchronise.  CBX_ERR_UNSUPPORTED: more than
  * one device, or cbx_set_force_split on; an update model other than
  * SYNCHRONOUSEAMSGD (3) with elastic averaging on (plain SMA takes
- * cbx_step_and_synchronise); gradient clipping on;
- * cbx_set_variable_learning_rates on with a multiplier that is not 1; Nesterov
+ * cbx_step_and_synchronise); gradient clipping on, or
+ * cbx_set_variable_learning_rates on with a multiplier that is not 1 (both take
+ * cbx_step_and_synchronise_elastic_clipped_variables below); Nesterov
  * momentum on a stepping replica; stepping replicas whose momentum or weight
  * decay differ.  CBX_ERR_STATE: replica momentum without a `last` buffer.
  * The launch shape is cbx_set_task_barrier_kernel_config's.                 */
 int cbx_step_and_synchronise_elastic (cbx_context *ctx, int first, int clock, int autotune,
                                       const int *tasks, void *const *streams, unsigned flags);
+/* cbx_step_and_synchronise_elastic for an EA-SGD context with gradient clipping
+ * (cbx_set_gradient_clip), per-variable learning rates
+ * (cbx_set_variable_learning_rates with a multiplier that is not 1), or both:
+ * what cbx_step_and_synchronise_clipped_variables is to the SMA barrier.  The
+ * parameters, the checks and their order are cbx_step_and_synchronise_elastic's;
+ * neither feature is refused.  Asynchronous.
+ *
+ * The norm passes are cbx_step_and_synchronise_clipped's: with clipping on, per
+ * stepping replica in id order on streams[id] where given, else on the sync
+ * stream, in front of the fused launch.  When no replica steps there is no norm
+ * pass and no record is touched.
+ *
+ * The arithmetic.  Per element of variable v and per participating replica i in
+ * ascending id order, one fp32 operation each:
+ *   stepping (tasks[id] >= 0), rate_i = -learning_rate (conf_i, tasks[id]):
+ *     g = scale_i * g                      clipping on: the record's scale, before weight decay
+ *     g = fma (wd, w, g)                   (wd > 0)
+ *     s = w                                (outputs kept)
+ *     r = rate_i * mult[v]                 per-variable rates on; else r = rate_i
+ *     g = r * g; g = fma (mu, last_i, g); last_i = g; w' = fma (1, g, w)   (mu > 0)
+ *     w' = fma (r, g, w)                                                   (mu = 0)
+ *     With the record's skip bit, s_i = w_i is a bit copy, g_i and last_i keep
+ *     every bit and w' = w_i.  Skipped wins over clipped.  With clipping on a
+ *     kept g_i is always written.
+ *   only joining: w' = w_i
+ *   all: d = fma (-1, z, w'); w_i = fma (-alpha, d, w'); acc = fma (alpha, d, acc)
+ * then z = fma (1, acc, z), acc starting from +0.  No base momentum and no
+ * Phase D, as in cbx_step_and_synchronise_elastic: copy flags are neither read
+ * nor cleared.
+ *
+ * The contract.  With flags == 0, z, every replica's w, s, g and `last`, every
+ * replica's cbx_clip_stats record and every piece of host state are left bit
+ * for bit as after
+ *   cbx_replica_optimise (ctx, id, tasks[id], streams[id])  (the same features on)
+ *                                     for every id with tasks[id] >= 0, in id order,
+ *   cbx_synchronise (ctx, first, clock, autotune, 0)
+ * under update model 3 with elastic averaging on.  With
+ * CBX_STEP_DISCARD_TASK_OUTPUTS, s_i and g_i of the stepping replicas are not
+ * written.  It moves (28R + 8) n bytes, (20R + 8) n with the discard flag, where
+ * the sequence moves (36R + 8) n; the norm passes add 4R n to each.
+ *
+ * With one feature off the call launches the kernel of the other; with both
+ * off, or with clipping alone and nobody stepping, it is
+ * cbx_step_and_synchronise_elastic: the same kernel, the same bits.
+ *
+ * Everything is checked before the first side effect: a refused call launches
+ * no norm pass and changes no buffer, flag, clock or record.  The refusals are
+ * cbx_step_and_synchronise_elastic's without the two features, and
+ * CBX_ERR_UNSUPPORTED with per-variable rates on for a model whose variables do
+ * not tile its elements and for a padded model too large for the chunk table;
+ * CBX_ERR_STATE for a stepping replica without clip scratch.                 */
+int cbx_step_and_synchronise_elastic_clipped_variables (cbx_context *ctx, int first, int clock, int autotune,
+                                                        const int *tasks, void *const *streams, unsigned flags);
 /* The pending task steps of the locked replicas and the one-GPU
  * synchronous-SGD barrier in one launch: cbx_step_and_synchronise for update
  * model WORKER (1; kernels/optimisers/synchronoussgd.cu:3-56 and
@@ -1430,6 +1484,49 @@ int cbx_ea_plan_step_and_optimise (cbx_sma_plan *plan, void *const *streams, flo
                                    int nreplicas, const int *replica_device,
                                    float *const *w, float *const *s, float *const *g, float *const *rlast,
                                    const int *locked, const int *step, const float *learning_rate,
+                                   float alpha, float replica_momentum, float weight_decay,
+                                   int first, unsigned flags);
+/* cbx_ea_plan_step_and_optimise with the stepping replicas' gradients clipped
+ * by global norm, a learning rate per variable, or both: what
+ * cbx_sma_plan_step_and_optimise_clipped_variables is to the SMA barrier, and
+ * cbx_step_and_synchronise_elastic_clipped_variables to a context.  The
+ * arguments of cbx_ea_plan_step_and_optimise mean the same.
+ * Clipping is on iff slot != NULL.  slot[id], max_norm and skip_nonfinite are
+ * cbx_sma_plan_step_and_optimise_clipped's: every stepping replica names a slot
+ * of its own in [0, 64), whose scratch is allocated on first use; its norm
+ * pass and reduce run on streams[0] in id order in front of the launch, and
+ * its record is read back with cbx_sma_plan_clip_stats.  max_norm == 0 with
+ * skip_nonfinite == 0 still reduces and counts.  When nobody steps there is no
+ * norm pass and no record is touched.
+ * use_variables is 0 or 1; with 1 the step of variable v uses
+ * learning_rate[id] * mult[v] of the table of cbx_sma_plan_set_variables.
+ * With slot == NULL and use_variables == 0 the call is
+ * cbx_ea_plan_step_and_optimise: the same kernel, the same bits.
+ * The contract.  With flags == 0 every buffer (z, every w, rlast, s and g) and
+ * every slot's record is left bit for bit as after, for every id with
+ * step[id] != 0 in id order,
+ *   clipping on:  cbx_sma_plan_optimise_clipped (plan, 0, slot[id], streams[0], w[id], g[id],
+ *                     rlast[id], s[id], learning_rate[id], replica_momentum, weight_decay,
+ *                     max_norm, skip_nonfinite, use_variables)
+ *   rates only:   cbx_sma_plan_optimise_variables (plan, 0, streams[0], w[id], g[id], rlast[id],
+ *                     s[id], learning_rate[id], replica_momentum, weight_decay, 0, nvars)
+ *   neither:      cbx_sma_optimise_buffers (...) as above
+ * and then cbx_ea_plan_step (plan, streams, z, nreplicas, replica_device, w,
+ * NULL, locked, alpha, first).  With the discard flag, s[id] and g[id] of the
+ * stepping replicas are not written.  Nothing at or past `elements` is read or
+ * written.  One-device, one-rank plans only.
+ * Everything is checked before the first launch.  CBX_ERR_INVALID: as
+ * cbx_ea_plan_step_and_optimise, and a max_norm that is negative, NaN or
+ * infinite, a skip_nonfinite or use_variables that is neither 0 nor 1, a
+ * stepping replica's slot out of range or named twice.  CBX_ERR_STATE:
+ * use_variables without a table.  CBX_ERR_UNSUPPORTED: a plan with more than
+ * one device or rank; more than 64 participating replicas.
+ * Returns CBX_OK or an error.                                              */
+int cbx_ea_plan_step_and_optimise_clipped_variables (cbx_sma_plan *plan, void *const *streams, float *const *z,
+                                   int nreplicas, const int *replica_device,
+                                   float *const *w, float *const *s, float *const *g, float *const *rlast,
+                                   const int *locked, const int *step, const float *learning_rate,
+                                   const int *slot, float max_norm, int skip_nonfinite, int use_variables,
                                    float alpha, float replica_momentum, float weight_decay,
                                    int first, unsigned flags);
 /* crossbowSynchronisationPolyakRuppert (synch/polyakruppert.c:319 -> :5-138

@@ -10,7 +10,7 @@ N=tests/native
   -Wl,-soname,libfakerccl.so -o "$N/libfakerccl.so.tmp" "$N/fake_rccl.cpp"
 mv "$N/libfakerccl.so.tmp" "$N/libfakerccl.so"
 # One object per source, compiled side by side ($MAX_JOBS at a time, else one per CPU, 16 at the most), then one link.
-SRCS="crossbow_amd/csrc/context.hip crossbow_amd/csrc/sync_steps.hip crossbow_amd/csrc/sma_kernels.hip crossbow_amd/csrc/averaging_kernels.hip crossbow_amd/csrc/sma_seam.hip crossbow_amd/csrc/stats_kernels.hip crossbow_amd/csrc/variable_rate_kernels.hip crossbow_amd/csrc/clip_kernels.hip crossbow_amd/csrc/task_barrier_kernels.hip crossbow_amd/csrc/task_barrier_variables_kernels.hip crossbow_amd/csrc/task_barrier_clipped_kernels.hip crossbow_amd/csrc/task_barrier_clipped_variables_kernels.hip crossbow_amd/csrc/task_elastic_kernels.hip crossbow_amd/csrc/task_ssgd_kernels.hip"
+SRCS="crossbow_amd/csrc/context.hip crossbow_amd/csrc/sync_steps.hip crossbow_amd/csrc/sma_kernels.hip crossbow_amd/csrc/averaging_kernels.hip crossbow_amd/csrc/sma_seam.hip crossbow_amd/csrc/stats_kernels.hip crossbow_amd/csrc/variable_rate_kernels.hip crossbow_amd/csrc/clip_kernels.hip crossbow_amd/csrc/task_barrier_kernels.hip crossbow_amd/csrc/task_barrier_variables_kernels.hip crossbow_amd/csrc/task_barrier_clipped_kernels.hip crossbow_amd/csrc/task_barrier_clipped_variables_kernels.hip crossbow_amd/csrc/task_elastic_kernels.hip crossbow_amd/csrc/task_ssgd_kernels.hip crossbow_amd/csrc/task_elastic_clipped_variables_kernels.hip crossbow_amd/csrc/task_elastic_clipped_kernels.hip crossbow_amd/csrc/task_elastic_variables_kernels.hip"
 JOBS=${MAX_JOBS:-$(nproc)}
 [ "$JOBS" -gt 16 ] && JOBS=16
 TMP=$(mktemp -d)

@@ -13,7 +13,7 @@ trap 'rm -rf "$TMP"' EXIT
 /opt/rocm/lib/llvm/bin/clang -c -O1 -g -std=c11 -fno-omit-frame-pointer -fsanitize=address,undefined \
   -I include -o "$TMP/abi_driver.o" tests/native/abi_driver.c
 # One object per source, compiled side by side ($MAX_JOBS at a time, else one per CPU, 16 at the most), then one link.
-SRCS="crossbow_amd/csrc/context.hip crossbow_amd/csrc/sync_steps.hip crossbow_amd/csrc/sma_kernels.hip crossbow_amd/csrc/averaging_kernels.hip crossbow_amd/csrc/sma_seam.hip crossbow_amd/csrc/stats_kernels.hip crossbow_amd/csrc/variable_rate_kernels.hip crossbow_amd/csrc/clip_kernels.hip crossbow_amd/csrc/task_barrier_kernels.hip crossbow_amd/csrc/task_barrier_variables_kernels.hip crossbow_amd/csrc/task_barrier_clipped_kernels.hip crossbow_amd/csrc/task_barrier_clipped_variables_kernels.hip crossbow_amd/csrc/task_elastic_kernels.hip crossbow_amd/csrc/task_ssgd_kernels.hip"
+SRCS="crossbow_amd/csrc/context.hip crossbow_amd/csrc/sync_steps.hip crossbow_amd/csrc/sma_kernels.hip crossbow_amd/csrc/averaging_kernels.hip crossbow_amd/csrc/sma_seam.hip crossbow_amd/csrc/stats_kernels.hip crossbow_amd/csrc/variable_rate_kernels.hip crossbow_amd/csrc/clip_kernels.hip crossbow_amd/csrc/task_barrier_kernels.hip crossbow_amd/csrc/task_barrier_variables_kernels.hip crossbow_amd/csrc/task_barrier_clipped_kernels.hip crossbow_amd/csrc/task_barrier_clipped_variables_kernels.hip crossbow_amd/csrc/task_elastic_kernels.hip crossbow_amd/csrc/task_ssgd_kernels.hip crossbow_amd/csrc/task_elastic_clipped_variables_kernels.hip crossbow_amd/csrc/task_elastic_clipped_kernels.hip crossbow_amd/csrc/task_elastic_variables_kernels.hip"
 JOBS=${MAX_JOBS:-$(nproc)}
 [ "$JOBS" -gt 16 ] && JOBS=16
 export TMP
