@@ -588,12 +588,20 @@ struct cbx_context {
   std::unique_ptr<cbx::host::EnqueuePool> pool;
   // The peer-read all-reduce with one process per GPU (cbx_peer_export /
   // cbx_peer_import, sync_steps.hip): every other rank's acc and D slots
-  // (Device::xslot) mapped here through IPC handles, and one page of completion flags in
-  // POSIX shared memory that every rank pins (hipHostRegister).  Rank h
-  // writes its flags from its streams (hipStreamWriteValue64: the step's
-  // sequence number once kernel A / the reduction of a bucket is done); the
-  // others' streams wait on them (hipStreamWaitValue64 >=).  The page is
-  // host memory: it needs no IPC mapping of its own (scripts/ipcprobe.hip).
+  // (Device::xslot) mapped here through IPC handles, and the completion
+  // flags.  Each rank keeps its own flag words (kIpcRankWords) in pinned host
+  // memory of its own (hipHostMalloc: memory a process already has cannot be
+  // pinned on every machine), which its host stores into directly and the
+  // other ranks map through its IPC handle, for their devices alone (an IPC
+  // mapping gives the host no address).  Rank h writes its flags from its
+  // streams (hipStreamWriteValue64: the step's sequence number once kernel A
+  // / the reduction of a bucket is done); the others' streams wait on them
+  // (hipStreamWaitValue64 >=).  What the hosts read of each other (done /
+  // opened / broken) lives on the hosts' page, POSIX shared memory that rank
+  // 0 creates: every rank's words in the same layout and, behind them, the
+  // IPC handle of each rank's flag words.  A rank's broken word is set in
+  // both; its flag words are copied to the hosts' page by cbx_wait once a
+  // release was written and the streams have drained.
   struct PeerIpc {
     bool ready = false;
     bool broken = false;                  // a step failed part-way: the flags were released
@@ -602,9 +610,11 @@ struct cbx_context {
     std::vector<const cbx::v4f *> acc;    // per rank: acc data (own: the local arena's)
     std::vector<const float *> acc_ctrl;  // per rank: acc control block
     std::vector<const cbx::v4f *> D;      // per rank: D data
-    void *page = nullptr;                 // the flag page, shared by every rank
+    void *page = nullptr;                 // the hosts' page, shared by every rank
     size_t page_bytes = 0;
-    uint64_t *dpage = nullptr;            // the same page as the device sees it
+    uint64_t *words = nullptr;            // this rank's flag words as its host sees them (hipHostMalloc)
+    std::vector<uint64_t *> dwords;       // per rank: its flag words as this rank's device sees them
+    hipStream_t host_stream = nullptr;    // teardown only: carries the release written on behalf of a dead peer
     bool owner = false;                   // rank 0 created the shared-memory object
     char shm_name[64] = {};
     uint64_t seq = 0;                     // split steps run in this form
@@ -1187,6 +1197,9 @@ void peer_close(cbx_context *c);
 // and so a broken word, came first).  Every
 // rank checks the words before each collective step and in cbx_wait
 // (peer_guard, peer_wait_check); cbx_resync_base clears them.
+// Where each word lives (cbx_context::PeerIpc): the streams read and write a
+// rank's own flag words (a[], r[], broken, poison); the hosts read done,
+// opened and broken on the hosts' page, which has the same layout per rank.
 constexpr int64_t kIpcMaxBuckets = 4096;
 constexpr size_t kIpcRankWords = 2 * kIpcMaxBuckets + 64;  // a[], r[], done + padding (512 B)
 // kIpcOpened: this rank's imports are done; kIpcBroken: a step of this rank

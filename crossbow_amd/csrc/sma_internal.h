@@ -278,10 +278,13 @@ hipError_t launch_sma_peer_reduce(const PeerArgs &p, const LaunchConfig &cfg, hi
 hipError_t launch_sma_peer_apply(const SmaArgs &a, const PeerArgs &p, bool momentum, const LaunchConfig &cfg,
                                  hipStream_t stream, Timing t = {});
 // One wave, after a per-rank peer-read step's last kernel B on the same
-// stream: if any of the G broken words (rank h's at broken + h * stride) is
-// set, store seq into *poison unless it already holds a step
-// (context_internal.h, kIpcPoison).
-hipError_t launch_peer_poison_check(const uint64_t *broken, int64_t stride, int G, uint64_t *poison, uint64_t seq,
+// stream: if any of the G broken words (rank h's at broken.word[h]: each
+// rank's words are an allocation of its own) is set, store seq into *poison
+// unless it already holds a step (context_internal.h, kIpcPoison).
+struct PeerBrokenWords {
+  const uint64_t *word[kMaxDevices];
+};
+hipError_t launch_peer_poison_check(const PeerBrokenWords &broken, int G, uint64_t *poison, uint64_t seq,
                                     hipStream_t stream);
 // The replica's local optimiser step of one task (the producer of s and w,
 // clib-multigpu/kernels/optimisers/sma.cu:3-100), fused into one pass.

@@ -571,13 +571,12 @@ __global__ __launch_bounds__(256) void sma_peer_apply_kernel(const SmaArgs a, co
 // and find the word set).  One wave per step: the check once per wave of
 // kernel B cost a PCIe read per wave, ~100 k small reads per step, and made
 // kernel B 40x slower (profiles/r06/rehearse_perrank_n2_wave_check.log).
-__global__ __launch_bounds__(64) void peer_poison_check_kernel(const uint64_t *broken, int64_t stride, int G,
-                                                               uint64_t *poison, uint64_t seq) {
+__global__ __launch_bounds__(64) void peer_poison_check_kernel(PeerBrokenWords broken, int G, uint64_t *poison,
+                                                               uint64_t seq) {
   const uint32_t lane = threadIdx.x & 63u;
   uint64_t v = 0;
   if (lane < (uint32_t)G)
-    v = __hip_atomic_load(const_cast<uint64_t *>(broken) + (int64_t)lane * stride, __ATOMIC_RELAXED,
-                          __HIP_MEMORY_SCOPE_SYSTEM);
+    v = __hip_atomic_load(const_cast<uint64_t *>(broken.word[lane]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   if (__builtin_amdgcn_ballot_w64(v != 0) != 0 && lane == 0 &&
       __hip_atomic_load(poison, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) == 0)
     __hip_atomic_store(poison, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -1153,10 +1152,12 @@ hipError_t launch_sma_peer_apply(const SmaArgs &a, const PeerArgs &p, bool momen
   return momentum ? peer_apply_u<true, 0>(a, p, cfg, stream, t) : peer_apply_u<false, 0>(a, p, cfg, stream, t);
 }
 
-hipError_t launch_peer_poison_check(const uint64_t *broken, int64_t stride, int G, uint64_t *poison, uint64_t seq,
+hipError_t launch_peer_poison_check(const PeerBrokenWords &broken, int G, uint64_t *poison, uint64_t seq,
                                     hipStream_t stream) {
-  if (!broken || !poison || G < 1 || G > 64) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(peer_poison_check_kernel, dim3(1), dim3(64), 0, stream, broken, stride, G, poison, seq);
+  if (!poison || G < 1 || G > kMaxDevices) return hipErrorInvalidValue;
+  for (int h = 0; h < G; ++h)
+    if (!broken.word[h]) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(peer_poison_check_kernel, dim3(1), dim3(64), 0, stream, broken, G, poison, seq);
   return hipGetLastError();
 }
 

@@ -147,14 +147,29 @@ struct PeerBlob {
   int64_t n4;
   uint64_t slot_bytes;
   hipIpcMemHandle_t acc, D;  // the base model's acc and D slots (control block first)
-  char shm[64];              // rank 0's: the flag page
+  char shm[64];              // rank 0's: the hosts' page
 };
 static_assert(sizeof(PeerBlob) <= CBX_PEER_BLOB_BYTES, "peer blob size");
 constexpr uint32_t kPeerMagic = 0x50584243u;  // "CBXP"
 
+// The hosts' page: every rank's words (ipc_word), then per rank the IPC
+// handle of its streams' words and whether it is there yet.
+struct WordsHandle {
+  hipIpcMemHandle_t handle;
+  uint64_t ready;
+};
+size_t flag_words_bytes(const cbx_context *c) { return (size_t)c->G * kIpcRankWords * sizeof(uint64_t); }
+volatile WordsHandle *words_handle(cbx_context *c, int rank) {
+  return reinterpret_cast<volatile WordsHandle *>(static_cast<char *>(c->ipc.page) + flag_words_bytes(c)) + rank;
+}
+// whole pages: hipIpcGetMemHandle refuses an allocation that is not (invalid argument)
+constexpr size_t kRankWordsBytes = (kIpcRankWords * sizeof(uint64_t) + 4095) / 4096 * 4096;
+
+// Maps the hosts' page (rank 0 creates it), allocates this rank's own words
+// for the streams and publishes their IPC handle on the hosts' page.
 int map_flag_page(cbx_context *c, bool create) {
   auto &p = c->ipc;
-  p.page_bytes = ((size_t)c->G * kIpcRankWords * sizeof(uint64_t) + 4095) / 4096 * 4096;
+  p.page_bytes = (flag_words_bytes(c) + (size_t)c->G * sizeof(WordsHandle) + 4095) / 4096 * 4096;
   const int fd = shm_open(p.shm_name, create ? (O_CREAT | O_EXCL | O_RDWR) : O_RDWR, 0600);
   if (fd < 0) return fail(CBX_ERR_IO, "shm_open(%s): %s", p.shm_name, strerror(errno));
   p.owner = create;
@@ -166,9 +181,19 @@ int map_flag_page(cbx_context *c, bool create) {
   close(fd);
   if (m == MAP_FAILED) return fail(CBX_ERR_IO, "mmap(%s): %s", p.shm_name, strerror(errno));
   p.page = m;  // a new object reads zero: no flag set yet
+  p.me = c->devs[0].g;
   HIP_TRY(hipSetDevice(c->devs[0].hip_id));
-  HIP_TRY(hipHostRegister(p.page, p.page_bytes, hipHostRegisterMapped | hipHostRegisterPortable));
-  HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&p.dpage), p.page, 0));
+  HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&p.words), kRankWordsBytes,
+                        hipHostMallocMapped | hipHostMallocPortable));
+  std::memset(p.words, 0, kRankWordsBytes);
+  p.dwords.assign((size_t)c->G, nullptr);
+  HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&p.dwords[p.me]), p.words, 0));
+  hipIpcMemHandle_t h;
+  HIP_TRY(hipIpcGetMemHandle(&h, p.dwords[p.me]));
+  std::memcpy(const_cast<hipIpcMemHandle_t *>(&words_handle(c, p.me)->handle), &h, sizeof(h));
+  __atomic_thread_fence(__ATOMIC_SEQ_CST);
+  words_handle(c, p.me)->ready = 1;
+  __atomic_thread_fence(__ATOMIC_SEQ_CST);
   return CBX_OK;
 }
 
@@ -181,15 +206,25 @@ std::string fmt_msg(const char *f, ...) {
   return buf;
 }
 
+// A word of the hosts' page (plain shared memory: no stream sees it).
 volatile uint64_t *host_word(cbx_context *c, int rank, int kind, int64_t b) {
   return static_cast<volatile uint64_t *>(c->ipc.page) + ipc_word(rank, kind, b);
+}
+// A word of this rank's own words, which its host stores into directly, and
+// a word of any rank's as this rank's device sees it.
+volatile uint64_t *own_word(cbx_context *c, int kind, int64_t b) {
+  return static_cast<volatile uint64_t *>(c->ipc.words) + ipc_word(0, kind, b);
+}
+uint64_t *stream_word(cbx_context *c, int rank, int kind, int64_t b) {
+  return c->ipc.dwords[(size_t)rank] + ipc_word(0, kind, b);
 }
 
 // A step that failed part-way, or one refused because another rank's failed:
 // no other rank may wait on this one's flags forever, and none may run
-// another step against it.  The host raises the rank's broken word (every
-// rank checks the page before its next collective step, peer_guard, and each
-// step's poison check after its last kernel B reads it, kIpcPoison), and only
+// another step against it.  The host raises the rank's broken word, on the
+// hosts' page (every rank checks it before its next collective step,
+// peer_guard) and in the rank's own words (each step's poison check after
+// its last kernel B reads it, kIpcPoison), and only
 // then writes the release value into every flag word of this rank (a peer
 // stream waiting on one goes on: whatever such a wait lets a kernel read, the
 // broken word was set before it).  The
@@ -205,22 +240,31 @@ void release_flags(cbx_context *c, int64_t nb, bool broken = true) {
   auto &p = c->ipc;
   if (!p.page) return;
   if (broken) {
-    *host_word(c, p.me, kIpcBroken, 0) = 1;
+    *host_word(c, p.me, kIpcBroken, 0) = 1;  // for the hosts
+    if (p.words) *own_word(c, kIpcBroken, 0) = 1;  // for every rank's poison check
     __atomic_thread_fence(__ATOMIC_SEQ_CST);
   }
+  p.released = true;
+  if (!p.words) return;
   for (int64_t b = 0; b < kIpcMaxBuckets; ++b) {
-    *host_word(c, p.me, kIpcA, b) = kIpcRelease;
-    *host_word(c, p.me, kIpcR, b) = kIpcRelease;
+    *own_word(c, kIpcA, b) = kIpcRelease;
+    *own_word(c, kIpcR, b) = kIpcRelease;
   }
   __atomic_thread_fence(__ATOMIC_SEQ_CST);
-  p.released = true;
-  if (nb <= 0 || !p.dpage) return;
+  if (nb <= 0) return;
   Device &d = c->devs[0];
   (void)hipSetDevice(d.hip_id);
   for (hipStream_t s : {d.stream, d.comm_stream, d.a_stream, d.a_stream2})
     for (int64_t b = 0; s && b < std::min(nb, kIpcMaxBuckets); ++b)
       for (int kind : {kIpcA, kIpcR})
-        (void)hipStreamWriteValue64(s, p.dpage + ipc_word(p.me, kind, b), kIpcRelease, 0);
+        (void)hipStreamWriteValue64(s, stream_word(c, p.me, kind, b), kIpcRelease, 0);
+}
+
+// Every rank's broken word as this rank's device sees it (the poison check's input).
+cbx::PeerBrokenWords broken_words(cbx_context *c) {
+  cbx::PeerBrokenWords w = {};
+  for (int h = 0; h < c->G; ++h) w.word[h] = stream_word(c, h, kIpcBroken, 0);
+  return w;
 }
 
 // The first rank whose broken word is set (a step of it failed part-way or
@@ -261,7 +305,7 @@ int peer_guard(cbx_context *c, const char *what) {
   // never run must go on: release them, whatever this call was.
   if (!p.released) release_flags(c, p.max_nb);
   p.broken = true;
-  const uint64_t poisoned = *host_word(c, p.me, kIpcPoison, 0);
+  const uint64_t poisoned = *own_word(c, kIpcPoison, 0);
   return fail(CBX_ERR_STATE, "%s refused: a per-rank peer-read step failed part-way earlier on this or another rank "
               "(rank %d's broken word is set; flags released)%s; z / last may differ across ranks, so every "
               "collective step is refused until cbx_resync_base", what, h < 0 ? p.me : h,
@@ -272,7 +316,17 @@ int peer_guard(cbx_context *c, const char *what) {
 int peer_wait_check(cbx_context *c) {
   auto &p = c->ipc;
   if (!p.ready) return CBX_OK;
-  const uint64_t poisoned = *host_word(c, p.me, kIpcPoison, 0);
+  if (p.released && drain_polled(c, 2))
+    // Every stream has drained (cbx_wait waited for the sync stream; the
+    // others get 2 s): what they and the release left in this rank's flag
+    // words goes on the hosts' page, where a post-mortem can read it.  Only
+    // the words the streams write show whether a queued write of a sequence
+    // number landed after the release.
+    for (int64_t b = 0; b < kIpcMaxBuckets; ++b) {
+      *host_word(c, p.me, kIpcA, b) = *own_word(c, kIpcA, b);
+      *host_word(c, p.me, kIpcR, b) = *own_word(c, kIpcR, b);
+    }
+  const uint64_t poisoned = *own_word(c, kIpcPoison, 0);
   if (poisoned == 0) return CBX_OK;
   if (!p.released) release_flags(c, p.max_nb);
   p.broken = true;
@@ -292,9 +346,8 @@ int resync_base(cbx_context *c, int root) {
   TRY(flush_task_waits(c));
   auto &p = c->ipc;
   if (p.ready && !p.released) {
-    bool known = p.broken || any_rank_broken(c);
-    for (int h = 0; h < c->G && !known; ++h) known = *host_word(c, h, kIpcPoison, 0) != 0;
-    if (known) release_flags(c, p.max_nb);
+    // (a rank's poison word is set only after some rank's broken word)
+    if (p.broken || any_rank_broken(c)) release_flags(c, p.max_nb);
   }
   if (!drain_polled(c, 60))
     return fail(CBX_ERR_STATE, "cbx_resync_base: this rank's streams are still busy after 60 s (a rank that never "
@@ -327,11 +380,11 @@ int resync_base(cbx_context *c, int root) {
   TRY(barrier());
   if (p.ready) {
     for (int64_t b = 0; b < kIpcMaxBuckets; ++b) {
-      *host_word(c, p.me, kIpcA, b) = 0;
-      *host_word(c, p.me, kIpcR, b) = 0;
+      *host_word(c, p.me, kIpcA, b) = *own_word(c, kIpcA, b) = 0;
+      *host_word(c, p.me, kIpcR, b) = *own_word(c, kIpcR, b) = 0;
     }
-    *host_word(c, p.me, kIpcPoison, 0) = 0;
-    *host_word(c, p.me, kIpcBroken, 0) = 0;
+    *own_word(c, kIpcPoison, 0) = 0;
+    *host_word(c, p.me, kIpcBroken, 0) = *own_word(c, kIpcBroken, 0) = 0;
     __atomic_thread_fence(__ATOMIC_SEQ_CST);
     TRY(barrier());
     p.seq = 0;  // every rank's next step in the form is number 1 again
@@ -426,44 +479,26 @@ int peer_import(cbx_context *c, const void *blobs, int nranks) {
   p.acc_ctrl.assign(nranks, nullptr);
   p.D.assign(nranks, nullptr);
   HIP_TRY(hipSetDevice(d.hip_id));
-  // The ranks open the others' handles one rank at a time; the others wait
-  // for the opener's "opened" word (a stream wait on the page, then
-  // hipStreamSynchronize).  The exporter's side of an open is served by a
-  // thread of the exporter's runtime (its IPC socket server), whatever the
-  // exporter's own threads do, so this order is not what makes an open
-  // complete: opens of a buffer of 2 GiB or more never complete under ROCm
-  // 7.0 (kIpcMaxSlotBytes), and export refuses those.  The
-  // order is kept because it was what the round-4 probes and tests ran, and
-  // it costs the import a few milliseconds per rank.
+  // The ranks open the others' handles one rank at a time; the others poll
+  // the opener's "opened" word on the hosts' page (the other ranks' flag
+  // words are themselves among the handles a rank opens in its turn).  The
+  // exporter's side of an open is served by a thread of the exporter's
+  // runtime (its IPC socket server), whatever the exporter's own threads do,
+  // so this order is not what makes an open complete: opens of a buffer of
+  // 2 GiB or more never complete under ROCm 7.0 (kIpcMaxSlotBytes, DESIGN.md
+  // 6), and export refuses those.  The order is kept because it was what the
+  // round-4 probes and tests ran, and it costs the import a few milliseconds
+  // per rank.
   // A rank that never takes its turn (it failed before, or died) must not
-  // park the others forever: 120 s after the import began (it takes
-  // seconds) a timer thread writes every awaited word itself, and the
-  // import fails.
-  hipStream_t park = nullptr;
-  HIP_TRY(hipStreamCreateWithFlags(&park, hipStreamNonBlocking));
+  // hold the others forever: 120 s after the import began (it takes
+  // seconds) they stop waiting for it, and the import fails.
   std::string err;
-  std::atomic<int> waiting_for{-1};
-  std::atomic<bool> finished{false}, timed_out{false};
   const auto deadline = std::chrono::steady_clock::now() + std::chrono::seconds(120);
-  std::thread timer([&] {
-    while (!finished.load(std::memory_order_acquire)) {
-      std::this_thread::sleep_for(std::chrono::milliseconds(10));
-      const int w = waiting_for.load(std::memory_order_acquire);
-      if (w >= 0 && std::chrono::steady_clock::now() > deadline) {
-        timed_out.store(true, std::memory_order_release);
-        *host_word(c, w, kIpcOpened, 0) = kIpcRelease;
-        __atomic_thread_fence(__ATOMIC_SEQ_CST);
-      }
-    }
-  });
   for (int r = 0; r < nranks; ++r) {
     if (r != p.me) {
-      waiting_for.store(r, std::memory_order_release);
-      hipError_t e = hipStreamWaitValue64(park, p.dpage + ipc_word(r, kIpcOpened, 0), 1, hipStreamWaitValueGte, ~0ull);
-      if (e == hipSuccess) e = hipStreamSynchronize(park);
-      waiting_for.store(-1, std::memory_order_release);
-      if (e != hipSuccess && err.empty()) err = fmt_msg("waiting for rank %d's turn: %s", r, hipGetErrorString(e));
-      if (timed_out.load(std::memory_order_acquire) && err.empty())
+      while (*host_word(c, r, kIpcOpened, 0) == 0 && std::chrono::steady_clock::now() < deadline)
+        std::this_thread::sleep_for(std::chrono::microseconds(100));
+      if (*host_word(c, r, kIpcOpened, 0) == 0 && err.empty())
         err = fmt_msg("rank %d had not opened its handles 120 s into the import", r);
       continue;
     }
@@ -476,6 +511,22 @@ int peer_import(cbx_context *c, const void *blobs, int nranks) {
       err = fmt_msg("fault injection: rank %d's opens fail ($CBX_FAULT_IPC_OPEN_FAIL)", p.me);
     for (int h = 0; h < nranks && err.empty(); ++h) {
       char *slot[2] = {d.xslot[0], d.xslot[1]};
+      if (h != p.me) {  // rank h's words, published when its import began
+        while (words_handle(c, h)->ready == 0 && std::chrono::steady_clock::now() < deadline)
+          std::this_thread::sleep_for(std::chrono::microseconds(100));
+        hipError_t e = hipErrorNotReady;
+        if (words_handle(c, h)->ready != 0) {
+          __atomic_thread_fence(__ATOMIC_SEQ_CST);
+          hipIpcMemHandle_t wh;
+          std::memcpy(&wh, const_cast<hipIpcMemHandle_t *>(&words_handle(c, h)->handle), sizeof(wh));
+          e = hipIpcOpenMemHandle(reinterpret_cast<void **>(&p.dwords[(size_t)h]), wh, hipIpcMemLazyEnablePeerAccess);
+        }
+        if (e != hipSuccess) {
+          p.dwords[(size_t)h] = nullptr;
+          err = fmt_msg("hipIpcOpenMemHandle(rank %d's flag words): %s", h, hipGetErrorString(e));
+          break;
+        }
+      }
       for (int k = 0; k < 2 && h != p.me; ++k) {
         void *m = nullptr;
         hipError_t e = hipIpcOpenMemHandle(&m, k == 0 ? pb[h].acc : pb[h].D, hipIpcMemLazyEnablePeerAccess);
@@ -495,9 +546,6 @@ int peer_import(cbx_context *c, const void *blobs, int nranks) {
     *host_word(c, p.me, kIpcOpened, 0) = err.empty() ? 1 : 2;
     __atomic_thread_fence(__ATOMIC_SEQ_CST);
   }
-  finished.store(true, std::memory_order_release);
-  timer.join();
-  (void)hipStreamDestroy(park);
   // Every rank's word is final here (this rank waited for each one's turn):
   // the import succeeds on every rank or on none, so no rank steps in the
   // form, or has its collective steps refused, because of another's failed
@@ -538,20 +586,25 @@ void peer_close(cbx_context *c) {
     drained = drain();
     if (!drained) {
       // This rank's streams wait on flags a peer will never write (it died
-      // mid-step): write the release into every rank's words on its behalf
-      // (the page is shared), so the waits end and the streams drain; the
-      // broken word first, so a step that the release lets run is reported
-      // by its poison check.
-      *host_word(c, p.me, kIpcBroken, 0) = 1;
-      __atomic_thread_fence(__ATOMIC_SEQ_CST);
-      for (int h = 0; h < c->G; ++h)
-        for (int64_t b = 0; b < kIpcMaxBuckets; ++b) {
-          *host_word(c, h, kIpcA, b) = kIpcRelease;
-          *host_word(c, h, kIpcR, b) = kIpcRelease;
-        }
-      __atomic_thread_fence(__ATOMIC_SEQ_CST);
+      // mid-step): write the release into every rank's words on its behalf,
+      // so the waits end and the streams drain; the broken word first, so a
+      // step that the release lets run is reported by its poison check.
+      // Only the device reaches another rank's words, so this rank's own
+      // released words (pinned, alive until they are freed below) are copied
+      // over them on a stream of its own.  Nothing waits for that copy: it
+      // may share a hardware queue with one of the parked streams and then
+      // lands no sooner than they move, in which case the 10 s below run
+      // out and everything is leaked as before.
+      release_flags(c, 0);
+      if (p.words && hipStreamCreateWithFlags(&p.host_stream, hipStreamNonBlocking) == hipSuccess)
+        for (int h = 0; h < c->G; ++h)
+          if (h != p.me && p.dwords[(size_t)h])
+            (void)hipMemcpyAsync(stream_word(c, h, kIpcA, 0), stream_word(c, p.me, kIpcA, 0),
+                                 2 * (size_t)kIpcMaxBuckets * sizeof(uint64_t), hipMemcpyDefault, p.host_stream);
       t0 = std::chrono::steady_clock::now() - std::chrono::seconds(50);  // 10 s more
       drained = drain();
+      while (drained && p.host_stream && hipStreamQuery(p.host_stream) == hipErrorNotReady)
+        if (!in_time()) drained = false;
     }
     if (drained) *host_word(c, p.me, kIpcDone, 0) = 1;
     __atomic_thread_fence(__ATOMIC_SEQ_CST);
@@ -568,15 +621,17 @@ void peer_close(cbx_context *c) {
   }
   if (!drained) {
     // Streams still queued against the others' memory: unmapping it (or the
-    // pinned page their waits read) under them would fault the device.  Leak
-    // the mappings and the page instead; the process is going down anyway.
-    // The name goes all the same: unlinking a mapped, pinned
-    // object only removes /dev/shm's entry, so no run leaves one behind.
+    // flag words their waits read) under them would fault the device.  Leak
+    // the mappings and the words instead; the process is going down anyway.
+    // The name goes all the same: unlinking a mapped object
+    // only removes /dev/shm's entry, so no run leaves one behind.
     release_flags(c, 0);
     if (p.owner) shm_unlink(p.shm_name);
     p.mapped.clear();
+    p.dwords.clear();
     p.page = nullptr;
-    p.dpage = nullptr;
+    p.words = nullptr;
+    p.host_stream = nullptr;
     p.ready = false;
     return;
   }
@@ -587,12 +642,21 @@ void peer_close(cbx_context *c) {
     // A rank still stepping when the meeting gave up must not take what it
     // reads next for a step's data: then the release marks this rank broken.
     release_flags(c, 0, !met);
-    (void)hipHostUnregister(p.page);
+    // The other ranks' words, then this rank's own.  A rank that never came
+    // to the meeting may still have streams waiting on these: its mapping
+    // keeps the pages (the allocation is gone once every mapping is), so
+    // what its waits read stays the release.
+    for (int h = 0; h < (int)p.dwords.size(); ++h)
+      if (h != p.me && p.dwords[(size_t)h]) (void)hipIpcCloseMemHandle(p.dwords[(size_t)h]);
+    if (p.words) (void)hipHostFree(p.words);
+    if (p.host_stream) (void)hipStreamDestroy(p.host_stream);
     munmap(p.page, p.page_bytes);
     if (p.owner) shm_unlink(p.shm_name);
   }
+  p.dwords.clear();
   p.page = nullptr;
-  p.dpage = nullptr;
+  p.words = nullptr;
+  p.host_stream = nullptr;
   p.ready = false;
 }
 
@@ -710,13 +774,13 @@ struct SplitStep {
   // work queued before it on `st` is; a wait holds `st` until rank h's flag
   // has reached this step.
   int put_flag(hipStream_t st, int kind, int64_t b) {
-    if (ipc) HIP_TRY(hipStreamWriteValue64(st, c->ipc.dpage + ipc_word(c->ipc.me, kind, b), seq, 0));
+    if (ipc) HIP_TRY(hipStreamWriteValue64(st, stream_word(c, c->ipc.me, kind, b), seq, 0));
     return CBX_OK;
   }
   int wait_flags(hipStream_t st, int kind, int64_t b) {
     for (int h = 0; ipc && !c->fault_skip_peer_wait && h < c->G; ++h)
       if (h != c->ipc.me)
-        HIP_TRY(hipStreamWaitValue64(st, c->ipc.dpage + ipc_word(h, kind, b), seq, hipStreamWaitValueGte, ~0ull));
+        HIP_TRY(hipStreamWaitValue64(st, stream_word(c, h, kind, b), seq, hipStreamWaitValueGte, ~0ull));
     return CBX_OK;
   }
 
@@ -1162,8 +1226,7 @@ struct SplitStep {
         for (int h = 0; h < p.G; ++h) p.D[h] = p_D(h) + start_of(b);
         HIP_TRY(cbx::launch_sma_peer_apply(a, p, mom, cfg, d.stream, t));
         if (ipc && b == nb - 1)  // every kernel B of the step is done before it (same stream)
-          HIP_TRY(cbx::launch_peer_poison_check(c->ipc.dpage + ipc_word(0, kIpcBroken, 0), (int64_t)kIpcRankWords,
-                                                c->G, c->ipc.dpage + ipc_word(c->ipc.me, kIpcPoison, 0), seq,
+          HIP_TRY(cbx::launch_peer_poison_check(broken_words(c), c->G, stream_word(c, c->ipc.me, kIpcPoison, 0), seq,
                                                 d.stream));
       } else {
         HIP_TRY(cbx::launch_sma_apply(a, mom && !rsag, cfg, d.stream, t));

@@ -966,16 +966,18 @@ int cbx_set_allreduce_algorithm (cbx_context *ctx, int algorithm);
  *      allocations of their own (below 2 GiB - 2 MiB each: ROCm 7.0's IPC
  *      keeps an allocation's size in 32 bits, and an open of 2 GiB or more
  *      never returns; CBX_ERR_UNSUPPORTED above); rank 0
- *      also creates the page of completion flags (POSIX shared memory) and
- *      names it in its blob;
+ *      also creates the hosts' page (POSIX shared memory, named in its
+ *      blob), on which the ranks' hosts meet;
  *   2. the caller gathers every rank's blob, in rank order, over its own
  *      control plane (bench.py: gloo all_gather);
  *   3. cbx_peer_import(ctx, blobs, nranks) maps every other rank's acc and
  *      D (hipIpcOpenMemHandle; the ranks open in turn; a rank that has not
  *      opened its handles 120 s into the import fails everyone's import) and
- *      pins the flag page
- *      (hipHostRegister).  It succeeds on every rank or on none: a rank
- *      whose opens failed fails every rank's import.
+ *      every other rank's completion flags: each rank keeps its own in
+ *      pinned host memory (hipHostMalloc; nothing is pinned after the
+ *      fact: not every machine can) and publishes their IPC handle on the
+ *      hosts' page.  It succeeds on every rank or on none: a rank whose
+ *      opens failed fails every rank's import.
  * Then CBX_ALLREDUCE_PEER is accepted.  The ranks' streams order each
  * other through the flags: a rank writes the step's sequence number after
  * its kernel A / reduction of a bucket (hipStreamWriteValue64), the others

@@ -2,8 +2,9 @@
 cbx_peer_import), G = 2, 3, 4, 8 rank processes on ONE GPU, the real library.
 
 Each rank maps every other rank's acc and D buffers through their IPC handles
-(hipIpcOpenMemHandle, dmabuf) and pins rank 0's page of completion flags
-(POSIX shared memory); the ranks' streams then order each other through the
+(hipIpcOpenMemHandle, dmabuf) and its completion flags (pinned host memory of
+the rank's own, hipHostMalloc; the hosts meet on a page in POSIX shared
+memory); the ranks' streams then order each other through the
 flags (hipStreamWriteValue64 after kernel A / the reduction of a bucket,
 hipStreamWaitValue64 >= this step's sequence number before reading another
 rank's acc or D).  Each rank also holds a real RCCL communicator
@@ -214,7 +215,10 @@ BLOB_SHM_OFFSET = 4 + 4 + 4 + 4 + 8 + 8 + 64 + 64  # PeerBlob.shm (sync_steps.hi
 
 def _flag_words(d: str, rank: int, nb: int):
     """Rank `rank`'s A and R words of buckets 0..nb-1 and its broken word,
-    read from the shared page (its name is in rank 0's exported blob)."""
+    read from the hosts' page (its name is in rank 0's exported blob).  The
+    A and R words there are the rank's own flag words, the ones its streams
+    write and the other ranks' streams wait on, as cbx_wait found them once
+    the rank had released them and its streams had drained."""
     blob = open(os.path.join(d, "peer_fail_0.bin"), "rb").read()
     name = blob[BLOB_SHM_OFFSET:BLOB_SHM_OFFSET + 64].split(b"\0")[0].decode()
     page = np.fromfile(os.path.join("/dev/shm", name.lstrip("/")), dtype=np.uint64)
