@@ -72,8 +72,8 @@ HEADERS = ("context_internal.h", "sma_internal.h", "stream_helpers.h", "stats_in
            "optimise_plan.h", "clip_internal.h", "bucket_pipeline.h", "task_ssgd_internal.h",
            # the fused task-step barrier's four kernel files are one text
            "task_barrier_step.h", "task_barrier_body.inc", "task_barrier_launch.h",
-           # and so are the three policy kernels of the fused elastic-averaging barrier
-           "task_elastic_policy.h", "task_elastic_policy_body.inc")
+           # and so are the four of the fused elastic-averaging barrier
+           "task_elastic_launch.h", "task_elastic_body.inc")
 
 
 def _sources(names=SOURCES):

@@ -735,6 +735,17 @@ static int check_fused_call(cbx_context *c, const char *me, int first, const int
   return CBX_OK;
 }
 
+// What conf.learning_rate would refuse, checked before any replica's query has
+// raised a flag.
+static int check_rate_policy(const SolverConf &conf) {
+  if (conf.policy == LR_STEP && conf.size <= 0) return fail(CBX_ERR_STATE, "step learning-rate policy with size 0");
+  if (conf.policy == LR_LSR && conf.warmuptasks <= 0) return fail(CBX_ERR_STATE, "LSR policy without warm-up tasks");
+  if (conf.policy == LR_CLR) return fail(CBX_ERR_UNSUPPORTED, "circular learning rate is unsupported");
+  if (conf.policy < LR_FIXED || conf.policy > LR_LSR)
+    return fail(CBX_ERR_UNSUPPORTED, "learning-rate policy %d unsupported", (int)conf.policy);
+  return CBX_OK;
+}
+
 // And last, once the call's own barrier and modes have passed: the stepping
 // replicas' configurations on the one device.  *ref_out is the first stepping
 // replica's (null: nobody steps); `clip`: every stepping replica needs its clip
@@ -756,12 +767,7 @@ static int check_stepping_replicas(cbx_context *c, const char *me, int first, co
       return fail(CBX_ERR_UNSUPPORTED, "%s: replica %d steps with momentum %g and weight decay %g, an earlier one with "
                   "%g and %g; one launch takes one pair", me, id, (double)conf.momentum, (double)conf.weightDecay,
                   (double)ref->momentum, (double)ref->weightDecay);
-    // what conf.learning_rate would refuse, before any replica's query has raised a flag
-    if (conf.policy == LR_STEP && conf.size <= 0) return fail(CBX_ERR_STATE, "step learning-rate policy with size 0");
-    if (conf.policy == LR_LSR && conf.warmuptasks <= 0) return fail(CBX_ERR_STATE, "LSR policy without warm-up tasks");
-    if (conf.policy == LR_CLR) return fail(CBX_ERR_UNSUPPORTED, "circular learning rate is unsupported");
-    if (conf.policy < LR_FIXED || conf.policy > LR_LSR)
-      return fail(CBX_ERR_UNSUPPORTED, "learning-rate policy %d unsupported", (int)conf.policy);
+    TRY(check_rate_policy(conf));
     if (clip && !c->replicas[id]->clip.dev) return fail(CBX_ERR_STATE, "replica %d has no gradient-clip scratch", id);
   }
   if (participating > cbx::kMaxReplicas)
@@ -795,6 +801,55 @@ static int launch_fused_norms(cbx_context *c, Device &d, const std::vector<Fused
   return CBX_OK;
 }
 
+// The stepping replicas' rates, in id order, into lr (one entry per replica).
+// A query may raise the replica's `_copy` (solverconfiguration.c:133,147): the
+// SMA call's Phase D honours it in the same call, the other barriers leave it
+// as they find it.
+static int query_rates(cbx_context *c, const int *tasks, std::vector<float> &lr) {
+  const int size = (int)lr.size();
+  for (int id = 0; id < size; ++id)
+    if (tasks[id] >= 0) TRY(c->replicas[id]->conf.learning_rate(tasks[id], &lr[(size_t)id]));
+  return CBX_OK;
+}
+
+namespace {
+// What a fused SMA or elastic call gathers of its stepping replicas beside the
+// launch's arguments.
+struct FusedSteps {
+  cbx::TaskBarrierArgs a;
+  cbx::ClipRecordPtrs records;
+  std::vector<hipStream_t> callers;
+  std::vector<FusedNorm> norms;  // the stepping replicas of a clipped call, id order
+  FusedSteps() {
+    std::memset(&a, 0, sizeof(a));
+    std::memset(&records, 0, sizeof(records));
+  }
+  // Replica r steps as participating replica k with learning rate lr, behind
+  // its gradient on the caller's stream `own` (null: the sync stream).  a.s[k]
+  // is the door's: the two barriers differ in whose s they read.
+  void step(Device &d, Replica &r, int k, float lr, void *own, bool clip) {
+    a.step_mask |= 1ull << k;
+    a.g[k] = reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_GRADIENT));
+    a.last[k] = r.conf.momentum > 0 ? reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_LAST)) : nullptr;
+    a.rate[k] = -lr;  // sma.cu:43
+    hipStream_t st = own ? reinterpret_cast<hipStream_t>(own) : d.stream;
+    if (st != d.stream && std::find(callers.begin(), callers.end(), st) == callers.end()) callers.push_back(st);
+    if (clip) {
+      records.p[k] = r.clip.record();
+      norms.push_back({&r, st});
+    }
+  }
+};
+}  // namespace
+
+// The launch comes after the gradients: one deferred wait per caller stream,
+// queued now, as cbx_synchronise queues the task steps' (DESIGN.md 7).
+static int defer_caller_waits(cbx_context *c, Device &d, const std::vector<hipStream_t> &callers) {
+  if (!c->fault_skip_task_wait)
+    for (hipStream_t st : callers) TRY(defer_task_wait(d, st));
+  return flush_task_waits(c);
+}
+
 static int step_and_synchronise(cbx_context *c, int first, int clock, int autotune, const int *tasks,
                                 void *const *streams, unsigned flags, FusedMode mode) {
   const bool variables = mode == FusedVariables || mode == FusedClippedVariables;
@@ -805,7 +860,6 @@ static int step_and_synchronise(cbx_context *c, int first, int clock, int autotu
                                                  : "cbx_step_and_synchronise";
   TraceRange trace(me);
   TRY(check_fused_call(c, me, first, tasks, flags));
-  const int size = c->size;
   const int type = c->model.type;
   if (type == CBX_UPDATE_SYNCHRONOUSEAMSGD && c->elastic_average)
     return fail(CBX_ERR_UNSUPPORTED, "%s: elastic averaging is on (cbx_set_elastic_average); only the SMA barrier is fused", me);
@@ -829,36 +883,18 @@ static int step_and_synchronise(cbx_context *c, int first, int clock, int autotu
   const SolverConf *ref = nullptr;  // the first stepping replica's configuration (null: nobody steps)
   TRY(check_stepping_replicas(c, me, first, tasks, clip, &ref));
 
-  // The rates, in id order: a query may raise the replica's `_copy`
-  // (solverconfiguration.c:133,147), which this same call's Phase D honours.
-  std::vector<float> lr((size_t)size, 0.0f);
-  for (int id = 0; id < size; ++id)
-    if (tasks[id] >= 0) TRY(c->replicas[id]->conf.learning_rate(tasks[id], &lr[(size_t)id]));
+  std::vector<float> lr((size_t)c->size, 0.0f);
+  TRY(query_rates(c, tasks, lr));  // a `_copy` raised here is honoured by this same call's Phase D
 
-  cbx::TaskBarrierArgs a;
-  std::memset(&a, 0, sizeof(a));
-  cbx::ClipRecordPtrs records;
-  std::memset(&records, 0, sizeof(records));
+  FusedSteps f;
+  cbx::TaskBarrierArgs &a = f.a;
   int k = 0, copies = 0;
-  std::vector<hipStream_t> callers;
-  std::vector<FusedNorm> norms;  // the stepping replicas of a clipped call, id order
   for (int id : d.replicas) {  // increasing id order, sma.c:69
     if (id < first || !c->locked[id]) continue;
     Replica &r = *c->replicas[id];
     a.w[k] = reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_DATA));
     a.s[k] = reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_DIFF));
-    if (tasks[id] >= 0) {
-      a.step_mask |= 1ull << k;
-      a.g[k] = reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_GRADIENT));
-      a.last[k] = r.conf.momentum > 0 ? reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_LAST)) : nullptr;
-      a.rate[k] = -lr[(size_t)id];  // sma.cu:43
-      hipStream_t st = streams && streams[id] ? reinterpret_cast<hipStream_t>(streams[id]) : d.stream;
-      if (st != d.stream && std::find(callers.begin(), callers.end(), st) == callers.end()) callers.push_back(st);
-      if (clip) {
-        records.p[k] = r.clip.record();
-        norms.push_back({&r, st});
-      }
-    }
+    if (tasks[id] >= 0) f.step(d, r, k, lr[(size_t)id], streams ? streams[id] : nullptr, clip);
     if (r.conf.copy) copies++;  // sma.c:113-120, after the queries
     ++k;
   }
@@ -872,29 +908,21 @@ static int step_and_synchronise(cbx_context *c, int first, int clock, int autotu
   a.wd = ref ? ref->weightDecay : 0.0f;
   a.copy = copies > 0 ? 1 : 0;
 
-  // The launch comes after the gradients: one deferred wait per caller stream,
-  // queued now, as cbx_synchronise queues the task steps' (DESIGN.md 7).
   HIP_TRY(hipSetDevice(d.hip_id));
   // the clipped call's norm passes, in front of the deferred waits
-  TRY(launch_fused_norms(c, d, norms));
-  if (!c->fault_skip_task_wait)
-    for (hipStream_t st : callers) TRY(defer_task_wait(d, st));
-  TRY(flush_task_waits(c));
+  TRY(launch_fused_norms(c, d, f.norms));
+  TRY(defer_caller_waits(c, d, f.callers));
   // A wait for a caller's stream now sits between the previous step and this
   // launch: its start is a marker of its own, not that step's stop
   // (step_start_event), as after cbx_replica_optimise on a task stream.
-  if (!callers.empty()) c->foreign_ops.fetch_add(1, std::memory_order_relaxed);
+  if (!f.callers.empty()) c->foreign_ops.fetch_add(1, std::memory_order_relaxed);
 
   cbx::LaunchConfig cfg = c->task_barrier_cfg;
   cfg.num_cus = d.num_cus;
   const bool keep = (flags & CBX_STEP_DISCARD_TASK_OUTPUTS) == 0;
   const cbx::Timing tm = {step_start_event(c, d, 0), step_stop_event(c, d, EV_A)};
-  // a clipped call in which no replica steps has nothing to clip: the per-variable or the plain kernel, the same bits
-  if (per_variable && !norms.empty())
-    HIP_TRY(cbx::launch_task_barrier_clipped_variables(a, d.var_tables_padded, records, keep, cfg, d.stream, tm));
-  else if (per_variable) HIP_TRY(cbx::launch_task_barrier_variables(a, d.var_tables_padded, keep, cfg, d.stream, tm));
-  else if (!norms.empty()) HIP_TRY(cbx::launch_task_barrier_clipped(a, records, keep, cfg, d.stream, tm));
-  else HIP_TRY(cbx::launch_task_barrier(a, keep, cfg, d.stream, tm));
+  HIP_TRY(cbx::pick_task_barrier_launch(a, per_variable ? &d.var_tables_padded : nullptr,
+                                        f.norms.empty() ? nullptr : &f.records, keep, cfg, d.stream, tm));
   close_fused_step(c, d);
   TRY(finish_sma_step(c, first));
   return finish_barrier(c, clock, autotune);
@@ -941,7 +969,6 @@ static int step_and_synchronise_elastic(cbx_context *c, int first, int clock, in
   const char *me = policies ? other : "cbx_step_and_synchronise_elastic";
   TraceRange trace(me);
   TRY(check_fused_call(c, me, first, tasks, flags));
-  const int size = c->size;
   const int type = c->model.type;
   if ((type == CBX_UPDATE_SMA || type == CBX_UPDATE_SYNCHRONOUSEAMSGD) && !c->elastic_average)
     return fail(CBX_ERR_UNSUPPORTED, "%s: elastic averaging is off (cbx_set_elastic_average); the SMA barrier takes "
@@ -965,35 +992,19 @@ static int step_and_synchronise_elastic(cbx_context *c, int first, int clock, in
   const SolverConf *ref = nullptr;  // the first stepping replica's configuration (null: nobody steps)
   TRY(check_stepping_replicas(c, me, first, tasks, clip, &ref));
 
-  // The rates, in id order: a query may raise the replica's `_copy`
-  // (solverconfiguration.c:133,147), which this barrier leaves as it finds it.
-  std::vector<float> lr((size_t)size, 0.0f);
-  for (int id = 0; id < size; ++id)
-    if (tasks[id] >= 0) TRY(c->replicas[id]->conf.learning_rate(tasks[id], &lr[(size_t)id]));
+  std::vector<float> lr((size_t)c->size, 0.0f);
+  TRY(query_rates(c, tasks, lr));
 
-  cbx::TaskBarrierArgs a;
-  std::memset(&a, 0, sizeof(a));
-  cbx::ClipRecordPtrs records;
-  std::memset(&records, 0, sizeof(records));
+  FusedSteps f;
+  cbx::TaskBarrierArgs &a = f.a;
   int k = 0;
-  std::vector<hipStream_t> callers;
-  std::vector<FusedNorm> norms;  // the stepping replicas of a clipped call, id order
   for (int id : d.replicas) {  // increasing id order, synchronouseamsgd.c:46
     if (id < first || !c->locked[id]) continue;
     Replica &r = *c->replicas[id];
     a.w[k] = reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_DATA));
     if (tasks[id] >= 0) {
-      a.step_mask |= 1ull << k;
       a.s[k] = reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_DIFF));
-      a.g[k] = reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_GRADIENT));
-      a.last[k] = r.conf.momentum > 0 ? reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_LAST)) : nullptr;
-      a.rate[k] = -lr[(size_t)id];  // sma.cu:43
-      hipStream_t st = streams && streams[id] ? reinterpret_cast<hipStream_t>(streams[id]) : d.stream;
-      if (st != d.stream && std::find(callers.begin(), callers.end(), st) == callers.end()) callers.push_back(st);
-      if (clip) {
-        records.p[k] = r.clip.record();
-        norms.push_back({&r, st});
-      }
+      f.step(d, r, k, lr[(size_t)id], streams ? streams[id] : nullptr, clip);
     }
     ++k;
   }
@@ -1004,14 +1015,10 @@ static int step_and_synchronise_elastic(cbx_context *c, int first, int clock, in
   a.momentum = ref ? ref->momentum : 0.0f;
   a.wd = ref ? ref->weightDecay : 0.0f;
 
-  // The launch comes after the gradients: one deferred wait per caller stream,
-  // queued now, as cbx_synchronise queues the task steps' (DESIGN.md 7).
   HIP_TRY(hipSetDevice(d.hip_id));
   // the clipped call's norm passes, in front of the deferred waits
-  TRY(launch_fused_norms(c, d, norms));
-  if (!c->fault_skip_task_wait)
-    for (hipStream_t st : callers) TRY(defer_task_wait(d, st));
-  TRY(flush_task_waits(c));
+  TRY(launch_fused_norms(c, d, f.norms));
+  TRY(defer_caller_waits(c, d, f.callers));
   // as cbx_synchronise counts a barrier that is not SMA's: its start is a marker of its own (step_start_event)
   c->foreign_ops.fetch_add(1, std::memory_order_relaxed);
 
@@ -1019,12 +1026,8 @@ static int step_and_synchronise_elastic(cbx_context *c, int first, int clock, in
   cfg.num_cus = d.num_cus;
   const bool keep = (flags & CBX_STEP_DISCARD_TASK_OUTPUTS) == 0;
   const cbx::Timing tm = {step_start_event(c, d, 0), step_stop_event(c, d, EV_A)};
-  // a clipped call in which no replica steps has nothing to clip: the per-variable or the plain kernel, the same bits
-  if (per_variable && !norms.empty())
-    HIP_TRY(cbx::launch_task_elastic_clipped_variables(a, d.var_tables_padded, records, keep, cfg, d.stream, tm));
-  else if (per_variable) HIP_TRY(cbx::launch_task_elastic_variables(a, d.var_tables_padded, keep, cfg, d.stream, tm));
-  else if (!norms.empty()) HIP_TRY(cbx::launch_task_elastic_clipped(a, records, keep, cfg, d.stream, tm));
-  else HIP_TRY(cbx::launch_task_elastic(a, keep, cfg, d.stream, tm));
+  HIP_TRY(cbx::pick_task_elastic_launch(a, per_variable ? &d.var_tables_padded : nullptr,
+                                        f.norms.empty() ? nullptr : &f.records, keep, cfg, d.stream, tm));
   close_fused_step(c, d);  // the ring slot, cross_valid = false: averaging_step's fused form
   TRY(finish_step(c));
   return finish_barrier(c, clock, autotune);
@@ -1086,22 +1089,11 @@ int cbx_step_and_synchronise_ssgd(cbx_context *c, int first, int clock, int auto
     return fail(CBX_ERR_UNSUPPORTED, "%s: more than %d locked replicas on one device; use %s", me, cbx::kMaxReplicas,
                 instead);
   if (c->model.wpc <= 0) return fail(CBX_ERR_STATE, "S-SGD needs the work per clock (setModelWorkPerClock)");
-  // what conf.learning_rate would refuse, before any replica's query has raised a flag
-  for (int id = 0; id < size; ++id) {
-    if (tasks[id] < 0) continue;
-    const SolverConf &conf = c->replicas[id]->conf;
-    if (conf.policy == LR_STEP && conf.size <= 0) return fail(CBX_ERR_STATE, "step learning-rate policy with size 0");
-    if (conf.policy == LR_LSR && conf.warmuptasks <= 0) return fail(CBX_ERR_STATE, "LSR policy without warm-up tasks");
-    if (conf.policy == LR_CLR) return fail(CBX_ERR_UNSUPPORTED, "circular learning rate is unsupported");
-    if (conf.policy < LR_FIXED || conf.policy > LR_LSR)
-      return fail(CBX_ERR_UNSUPPORTED, "learning-rate policy %d unsupported", (int)conf.policy);
-  }
-
-  // The rates, in id order: a query may raise the replica's `_copy`
-  // (solverconfiguration.c:133,147), which this barrier leaves as it finds it.
-  std::vector<float> lr((size_t)size, 0.0f);
   for (int id = 0; id < size; ++id)
-    if (tasks[id] >= 0) TRY(c->replicas[id]->conf.learning_rate(tasks[id], &lr[(size_t)id]));
+    if (tasks[id] >= 0) TRY(check_rate_policy(c->replicas[id]->conf));
+
+  std::vector<float> lr((size_t)size, 0.0f);
+  TRY(query_rates(c, tasks, lr));
 
   cbx::TaskSsgdArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -1127,12 +1119,8 @@ int cbx_step_and_synchronise_ssgd(cbx_context *c, int first, int clock, int auto
   a.ratio = (float)(1.0 / (double)(float)c->model.wpc);  // synchronoussgd.c:55
   a.momentum = mom ? c->model.conf.momentum : 0.0f;
 
-  // The launch comes after the gradients (synchronoussgd.cu:38-40): one deferred
-  // wait per caller stream, queued now, as cbx_synchronise queues the task steps'.
   HIP_TRY(hipSetDevice(d.hip_id));
-  if (!c->fault_skip_task_wait)
-    for (hipStream_t st : callers) TRY(defer_task_wait(d, st));
-  TRY(flush_task_waits(c));
+  TRY(defer_caller_waits(c, d, callers));  // the launch comes after the gradients (synchronoussgd.cu:38-40)
   // as cbx_synchronise counts a barrier that is not SMA's: its start is a marker of its own (step_start_event)
   c->foreign_ops.fetch_add(1, std::memory_order_relaxed);
 

@@ -385,6 +385,40 @@ hipError_t launch_task_barrier(const TaskBarrierArgs &a, bool keep_task_outputs,
 // tail with unroll 1 and policy 1.  Anything else is hipErrorInvalidValue.
 hipError_t launch_task_barrier_variables(const TaskBarrierArgs &a, const VarTables &t, bool keep_task_outputs,
                                          const LaunchConfig &cfg, hipStream_t stream, Timing tm = {});
+struct ClipRecordPtrs;  // clip_internal.h
+// launch_task_barrier with the clipped step (task_barrier_clipped_kernels.hip,
+// a shared object of its own: libcrossbow_sma_clipped.so): stepping replica k
+// multiplies g by the scale of rec.p[k] before weight decay, writes a kept g
+// always, and with the record's skip bit does s = w and nothing else before it
+// joins the barrier.  rec.p[k] is the record launch_gradient_norm left earlier
+// on the stream, non-null for every stepping replica; the other entries are not
+// read.  At least one replica steps (without one there is nothing to clip:
+// launch_task_barrier).  Compiled forms: no tail with unroll 1 or 2 and either
+// policy; a tail with unroll 1 and policy 1.  Anything else is
+// hipErrorInvalidValue, before the launch.
+hipError_t launch_task_barrier_clipped(const TaskBarrierArgs &a, const ClipRecordPtrs &rec, bool keep_task_outputs,
+                                       const LaunchConfig &cfg, hipStream_t stream, Timing t = {});
+// launch_task_barrier_clipped with a learning rate per variable
+// (task_barrier_clipped_variables_kernels.hip, a shared object of its own:
+// libcrossbow_sma_clipped_variables.so): stepping replica k clips as above and
+// steps with a.rate[k] * t.mult[v], launch_sma_optimise_variables_clipped's
+// bits per replica.  The tables as for launch_task_barrier_variables, the
+// records and the compiled forms as for launch_task_barrier_clipped.
+hipError_t launch_task_barrier_clipped_variables(const TaskBarrierArgs &a, const VarTables &t,
+                                                 const ClipRecordPtrs &rec, bool keep_task_outputs,
+                                                 const LaunchConfig &cfg, hipStream_t stream, Timing tm = {});
+// The one of the four launches above that a door's call comes to: `t` where
+// the step reads a learning rate per variable, `rec` where it clips, which a
+// call in which no replica steps does not (there is nothing to clip: the
+// per-variable or the plain kernel gives the same bits).
+static inline hipError_t pick_task_barrier_launch(const TaskBarrierArgs &a, const VarTables *t,
+                                                  const ClipRecordPtrs *rec, bool keep_task_outputs,
+                                                  const LaunchConfig &cfg, hipStream_t stream, Timing tm = {}) {
+  if (t && rec) return launch_task_barrier_clipped_variables(a, *t, *rec, keep_task_outputs, cfg, stream, tm);
+  if (t) return launch_task_barrier_variables(a, *t, keep_task_outputs, cfg, stream, tm);
+  if (rec) return launch_task_barrier_clipped(a, *rec, keep_task_outputs, cfg, stream, tm);
+  return launch_task_barrier(a, keep_task_outputs, cfg, stream, tm);
+}
 // One-wave blocks, one float4 per lane, auto occupancy (2 waves per CU at
 // R = 8): at the SMA step's own shape, two float4s per lane, it measured 2-5 %
 // slower in each of three runs (scripts/bench_step_and_synchronise.py --sweep,
@@ -411,7 +445,7 @@ hipError_t launch_task_elastic(const TaskBarrierArgs &a, bool keep_task_outputs,
                                hipStream_t stream, Timing t = {});
 // launch_task_elastic behind the three other step policies of
 // task_barrier_step.h (cbx_step_and_synchronise_elastic_clipped_variables,
-// cbx_ea_plan_step_and_optimise_clipped_variables; task_elastic_policy_body.inc
+// cbx_ea_plan_step_and_optimise_clipped_variables; task_elastic_body.inc
 // and the three task_elastic_*_kernels.hip, together a shared object of their
 // own: libcrossbow_sma_elastic_policies.so).  The step is that of the SMA
 // launch of the same policy (launch_task_barrier_variables,
@@ -421,7 +455,6 @@ hipError_t launch_task_elastic(const TaskBarrierArgs &a, bool keep_task_outputs,
 // replica has one, and a launch in which nobody steps is refused by the clipped
 // two.  The barrier, the compiled forms and everything else are
 // launch_task_elastic's.
-struct ClipRecordPtrs;  // clip_internal.h
 hipError_t launch_task_elastic_variables(const TaskBarrierArgs &a, const VarTables &t, bool keep_task_outputs,
                                          const LaunchConfig &cfg, hipStream_t stream, Timing tm = {});
 hipError_t launch_task_elastic_clipped(const TaskBarrierArgs &a, const ClipRecordPtrs &rec, bool keep_task_outputs,
@@ -429,6 +462,15 @@ hipError_t launch_task_elastic_clipped(const TaskBarrierArgs &a, const ClipRecor
 hipError_t launch_task_elastic_clipped_variables(const TaskBarrierArgs &a, const VarTables &t,
                                                  const ClipRecordPtrs &rec, bool keep_task_outputs,
                                                  const LaunchConfig &cfg, hipStream_t stream, Timing tm = {});
+// pick_task_barrier_launch's choice among the four elastic launches.
+static inline hipError_t pick_task_elastic_launch(const TaskBarrierArgs &a, const VarTables *t,
+                                                  const ClipRecordPtrs *rec, bool keep_task_outputs,
+                                                  const LaunchConfig &cfg, hipStream_t stream, Timing tm = {}) {
+  if (t && rec) return launch_task_elastic_clipped_variables(a, *t, *rec, keep_task_outputs, cfg, stream, tm);
+  if (t) return launch_task_elastic_variables(a, *t, keep_task_outputs, cfg, stream, tm);
+  if (rec) return launch_task_elastic_clipped(a, *rec, keep_task_outputs, cfg, stream, tm);
+  return launch_task_elastic(a, keep_task_outputs, cfg, stream, tm);
+}
 // DEFAULT update model (0, kernels/optimisers/default.cu:3-131): the task
 // step moves the replica and its device's base model by the same gradient.
 // Reads w, g (, last), z; writes g (if changed), last, w, z.

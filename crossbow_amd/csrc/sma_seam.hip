@@ -514,6 +514,38 @@ struct SeamClip {
 };
 }  // namespace
 
+// Stepping replica id's slot of a clipped call: in range, and no other stepping
+// replica's in this call (*taken holds one bit per slot).
+static int take_clip_slot(const char *me, int id, int sl, uint64_t *taken) {
+  static_assert(cbx_sma_plan::kClipSlots <= 64, "one bit per slot");
+  if (sl < 0 || sl >= cbx_sma_plan::kClipSlots)
+    return fail(CBX_ERR_INVALID, "%s: stepping replica %d: slot %d out of range [0, %d)", me, id, sl,
+                cbx_sma_plan::kClipSlots);
+  if ((*taken >> sl) & 1ull)
+    return fail(CBX_ERR_INVALID, "%s: stepping replica %d: slot %d is another stepping replica's", me, id, sl);
+  *taken |= 1ull << sl;
+  return CBX_OK;
+}
+
+// The norm passes of a clipped call in id order on the launch's stream, each
+// over its slot's scratch (allocated on first use), as
+// cbx_sma_plan_optimise_clipped runs them: the records are the sequence's bits.
+// slot_of[k]: the slot of participating replica k, or -1.  No wait is queued.
+static int plan_norm_passes(cbx_sma_plan *p, const char *me, const cbx::TaskBarrierArgs &a, const int *slot_of,
+                            const SeamClip &clip, hipStream_t stream, cbx::ClipRecordPtrs &records) {
+  std::memset(&records, 0, sizeof(records));
+  cbx::ClipScratch *cs[cbx::kMaxReplicas] = {};
+  for (int k = 0; k < a.nrep; ++k)  // every scratch before the first launch: a failed allocation bumps no counter
+    if (slot_of[k] >= 0) TRY(clip_slot(p, me, 0, slot_of[k], &cs[k]));
+  for (int k = 0; k < a.nrep; ++k) {
+    if (!cs[k]) continue;
+    HIP_TRY(cbx::launch_gradient_norm(reinterpret_cast<const float *>(a.g[k]), p->n, *cs[k], clip.max_norm,
+                                      clip.skip_nonfinite == 1, p->clip_norm_policy, stream));
+    records.p[k] = cs[k]->record();
+  }
+  return CBX_OK;
+}
+
 static int plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *const *z, float *const *last,
                                   int nreplicas, const int *replica_device, float *const *w, float *const *s,
                                   float *const *g, float *const *rlast, const int *locked, const int *copy,
@@ -559,7 +591,6 @@ static int plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *
   bool steps = false;
   int slot_of[cbx::kMaxReplicas];  // clipped: the slot of participating replica k, or -1
   uint64_t slots_taken = 0;
-  static_assert(cbx_sma_plan::kClipSlots <= 64, "one bit per slot");
   for (int id = first; id < nreplicas; ++id) {  // increasing id order, sma.c:69
     if (!locked[id]) continue;
     if (replica_device[id] != 0) return fail(CBX_ERR_INVALID, "%s: replica %d on device %d of 1", me, id, replica_device[id]);
@@ -574,13 +605,7 @@ static int plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *
       return fail(CBX_ERR_INVALID, "%s: stepping replica %d: replica momentum > 0 needs a 16-byte aligned last buffer", me, id);
     if (clipped && st) {
       if (!clip.slot) return fail(CBX_ERR_INVALID, "%s: stepping replica %d without a slot list", me, id);
-      const int sl = clip.slot[id];
-      if (sl < 0 || sl >= cbx_sma_plan::kClipSlots)
-        return fail(CBX_ERR_INVALID, "%s: stepping replica %d: slot %d out of range [0, %d)", me, id, sl,
-                    cbx_sma_plan::kClipSlots);
-      if ((slots_taken >> sl) & 1ull)
-        return fail(CBX_ERR_INVALID, "%s: stepping replica %d: slot %d is another stepping replica's", me, id, sl);
-      slots_taken |= 1ull << sl;
+      TRY(take_clip_slot(me, id, clip.slot[id], &slots_taken));
     }
     if (++participating > cbx::kMaxReplicas) continue;  // counted on, refused below
     const int k = a.nrep++;
@@ -612,33 +637,12 @@ static int plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *
   HIP_TRY(hipSetDevice(d.hip_id));
   cbx::LaunchConfig cfg = p->task_barrier_cfg;
   cfg.num_cus = d.num_cus;
-  if (clipped && steps) {
-    // The norm passes in id order on the launch's stream, each over its slot's
-    // scratch (allocated on first use), as cbx_sma_plan_optimise_clipped runs
-    // them: the records are the sequence's bits.  No wait is queued.
-    cbx::ClipRecordPtrs records;
-    std::memset(&records, 0, sizeof(records));
-    cbx::ClipScratch *cs[cbx::kMaxReplicas] = {};
-    for (int k = 0; k < a.nrep; ++k)  // every scratch before the first launch: a failed allocation bumps no counter
-      if (slot_of[k] >= 0) TRY(clip_slot(p, me, 0, slot_of[k], &cs[k]));
-    for (int k = 0; k < a.nrep; ++k) {
-      if (!cs[k]) continue;
-      HIP_TRY(cbx::launch_gradient_norm(reinterpret_cast<const float *>(a.g[k]), p->n, *cs[k], clip.max_norm,
-                                        clip.skip_nonfinite == 1, p->clip_norm_policy,
-                                        static_cast<hipStream_t>(streams[0])));
-      records.p[k] = cs[k]->record();
-    }
-    if (variables)
-      HIP_TRY(cbx::launch_task_barrier_clipped_variables(a, d.var_tables, records, keep, cfg,
-                                                         static_cast<hipStream_t>(streams[0]), p->next_timing()));
-    else
-      HIP_TRY(cbx::launch_task_barrier_clipped(a, records, keep, cfg, static_cast<hipStream_t>(streams[0]),
-                                               p->next_timing()));
-  } else if (variables)
-    HIP_TRY(cbx::launch_task_barrier_variables(a, d.var_tables, keep, cfg, static_cast<hipStream_t>(streams[0]),
-                                               p->next_timing()));
-  else
-    HIP_TRY(cbx::launch_task_barrier(a, keep, cfg, static_cast<hipStream_t>(streams[0]), p->next_timing()));
+  hipStream_t st0 = static_cast<hipStream_t>(streams[0]);
+  cbx::ClipRecordPtrs records;
+  const bool clips = clipped && steps;  // nobody steps: nothing to clip
+  if (clips) TRY(plan_norm_passes(p, me, a, slot_of, clip, st0, records));
+  HIP_TRY(cbx::pick_task_barrier_launch(a, variables ? &d.var_tables : nullptr, clips ? &records : nullptr, keep, cfg,
+                                        st0, p->next_timing()));
   return copies > 0 ? 1 : 0;
 }
 
@@ -762,15 +766,7 @@ static int ea_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, floa
       return fail(CBX_ERR_INVALID, "%s: stepping replica %d: g must be non-null and 16-byte aligned", me, id);
     if (st && rmom && (!rlast[id] || !aligned16(rlast[id])))
       return fail(CBX_ERR_INVALID, "%s: stepping replica %d: replica momentum > 0 needs a 16-byte aligned last buffer", me, id);
-    if (clipped && st) {
-      const int sl = clip.slot[id];
-      if (sl < 0 || sl >= cbx_sma_plan::kClipSlots)
-        return fail(CBX_ERR_INVALID, "%s: stepping replica %d: slot %d out of range [0, %d)", me, id, sl,
-                    cbx_sma_plan::kClipSlots);
-      if ((slots_taken >> sl) & 1ull)
-        return fail(CBX_ERR_INVALID, "%s: stepping replica %d: slot %d is another stepping replica's", me, id, sl);
-      slots_taken |= 1ull << sl;
-    }
+    if (clipped && st) TRY(take_clip_slot(me, id, clip.slot[id], &slots_taken));
     if (++participating > cbx::kMaxReplicas) continue;  // counted on, refused below
     const int k = a.nrep++;
     slot_of[k] = clipped && st ? clip.slot[id] : -1;
@@ -799,27 +795,11 @@ static int ea_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, floa
   cbx::LaunchConfig cfg = p->task_barrier_cfg;
   cfg.num_cus = d.num_cus;
   hipStream_t st0 = static_cast<hipStream_t>(streams[0]);
-  if (clipped && steps) {
-    // The norm passes in id order on the launch's stream, each over its slot's
-    // scratch (allocated on first use), as cbx_sma_plan_optimise_clipped runs
-    // them: the records are the sequence's bits.  No wait is queued.
-    cbx::ClipRecordPtrs records;
-    std::memset(&records, 0, sizeof(records));
-    cbx::ClipScratch *cs[cbx::kMaxReplicas] = {};
-    for (int k = 0; k < a.nrep; ++k)  // every scratch before the first launch: a failed allocation bumps no counter
-      if (slot_of[k] >= 0) TRY(clip_slot(p, me, 0, slot_of[k], &cs[k]));
-    for (int k = 0; k < a.nrep; ++k) {
-      if (!cs[k]) continue;
-      HIP_TRY(cbx::launch_gradient_norm(reinterpret_cast<const float *>(a.g[k]), p->n, *cs[k], clip.max_norm,
-                                        clip.skip_nonfinite == 1, p->clip_norm_policy, st0));
-      records.p[k] = cs[k]->record();
-    }
-    if (variables) HIP_TRY(cbx::launch_task_elastic_clipped_variables(a, d.var_tables, records, keep, cfg, st0, p->next_timing()));
-    else HIP_TRY(cbx::launch_task_elastic_clipped(a, records, keep, cfg, st0, p->next_timing()));
-  } else if (variables)
-    HIP_TRY(cbx::launch_task_elastic_variables(a, d.var_tables, keep, cfg, st0, p->next_timing()));
-  else
-    HIP_TRY(cbx::launch_task_elastic(a, keep, cfg, st0, p->next_timing()));
+  cbx::ClipRecordPtrs records;
+  const bool clips = clipped && steps;  // nobody steps: nothing to clip
+  if (clips) TRY(plan_norm_passes(p, me, a, slot_of, clip, st0, records));
+  HIP_TRY(cbx::pick_task_elastic_launch(a, variables ? &d.var_tables : nullptr, clips ? &records : nullptr, keep, cfg,
+                                        st0, p->next_timing()));
   return CBX_OK;
 }
 

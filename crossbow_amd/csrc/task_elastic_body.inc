@@ -1,9 +1,10 @@
-// task_elastic_policy_body.inc -- the body of the three fused task-step
-// elastic-averaging kernels that have a step policy (task_elastic_variables_kernels.hip,
-// task_elastic_clipped_kernels.hip, task_elastic_clipped_variables_kernels.hip),
-// included inside each of them behind its policy `step` (task_barrier_step.h).
-// It is task_elastic_kernel's loop (task_elastic_kernels.hip) with the policy
-// members of task_barrier_body.inc, and shared as text for that file's reason.
+// task_elastic_body.inc -- the body of the four fused task-step
+// elastic-averaging kernels (task_elastic_kernels.hip,
+// task_elastic_variables_kernels.hip, task_elastic_clipped_kernels.hip,
+// task_elastic_clipped_variables_kernels.hip), included inside each of them
+// behind its policy `step` (task_barrier_step.h).  The policy members are
+// those of task_barrier_body.inc, and the text is shared as text for that
+// file's reason.
 //
 // In scope: the kernel's template parameters R, MIXED, MOM, WD, KEEP, P, TAIL,
 // U, its parameter `a` (TaskBarrierArgs) and `step`.
@@ -22,12 +23,16 @@
 //   only joining: w' = w_i
 //   all: d = fma(-1, z, w') ; w_i = fma(-alpha, d, w') ; acc = fma(alpha, d, acc)   synchronouseamsgd.c:55-77
 // then z = fma(1, acc, z) (:85-90), acc from +0 (:43).
+//
+// Unlike the SMA fused kernel (task_barrier_body.inc): d comes from the stepped
+// w', not from a snapshot; a replica that only joins is one stream, not two;
+// there is no base momentum and no Phase D, and no copy flag is looked at.
 {
   typedef decltype(step) STEP;
   constexpr int RR = (R > 0) ? R : kChunk;
   if constexpr (TAIL) {
     if (blockIdx.x < (uint32_t)a.tail_blocks) {
-      task_elastic_policy_tail_elem<MOM, WD, KEEP>(a, step);
+      task_elastic_tail_elem<MOM, WD, KEEP>(a, step);
       return;
     }
   }

@@ -5,15 +5,15 @@
 // CDNA4 (gfx950).
 //
 // task_elastic_kernel (task_elastic_kernels.hip) with the CLIP arithmetic of
-// sma_optimise_kernel: the shared text (task_elastic_policy_body.inc,
-// task_elastic_policy.h) behind the ClippedStep policy.  The record pointers
+// sma_optimise_kernel: the shared text (task_elastic_body.inc,
+// task_elastic_launch.h) behind the ClippedStep policy.  The record pointers
 // are a kernel parameter of their own beside TaskBarrierArgs.
 //
 // One of the three compilation units of libcrossbow_sma_elastic_policies.so:
 // the device code of the other shared objects is not touched by it.
 #include <hip/hip_ext.h>
 
-#include "task_elastic_policy.h"
+#include "task_elastic_launch.h"
 
 namespace cbx {
 
@@ -27,7 +27,7 @@ namespace {
 template <int R, bool MIXED, bool MOM, bool WD, bool KEEP, int P, bool TAIL, int U>
 __global__ __launch_bounds__(256) void task_elastic_clipped_kernel(const TaskBarrierArgs a, const ClipRecordPtrs rec) {
   const typename step_policy<ClippedStep, R>::type step{rec};
-#include "task_elastic_policy_body.inc"
+#include "task_elastic_body.inc"
 }
 
 struct ElasticClippedLauncher {
@@ -48,7 +48,7 @@ hipError_t launch_task_elastic_clipped(const TaskBarrierArgs &a, const ClipRecor
   // the replicas that only join hold a valid one: the kernel loads them all
   ClipRecordPtrs full;
   if (!task_barrier_fill_records(a, rec, full)) return hipErrorInvalidValue;
-  return task_elastic_policy_launch(ElasticClippedLauncher{full}, a, keep_task_outputs, cfg, stream, t);
+  return task_elastic_launch(ElasticClippedLauncher{full}, a, keep_task_outputs, cfg, stream, t);
 }
 
 }  // namespace cbx

@@ -7,7 +7,7 @@
 //
 // task_elastic_kernel (task_elastic_kernels.hip) with both the CLIP arithmetic
 // of sma_optimise_kernel and the rate lookup of sma_optimise_variables_kernel:
-// the shared text (task_elastic_policy_body.inc, task_elastic_policy.h) behind
+// the shared text (task_elastic_body.inc, task_elastic_launch.h) behind
 // the ClippedVariablesStep policy.  The tables and the record pointers are
 // kernel parameters of their own beside TaskBarrierArgs.
 //
@@ -15,7 +15,7 @@
 // the device code of the other shared objects is not touched by it.
 #include <hip/hip_ext.h>
 
-#include "task_elastic_policy.h"
+#include "task_elastic_launch.h"
 
 namespace cbx {
 
@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void task_elastic_clipped_variables_kernel(con
                                                                              const uint32_t nvars,
                                                                              const ClipRecordPtrs rec) {
   const typename step_policy<ClippedVariablesStep, R>::type step{chunks, bounds, mult, nvars, rec};
-#include "task_elastic_policy_body.inc"
+#include "task_elastic_body.inc"
 }
 
 struct ElasticClippedVariablesLauncher {
@@ -56,7 +56,7 @@ hipError_t launch_task_elastic_clipped_variables(const TaskBarrierArgs &a, const
   if (!task_barrier_tables_cover(a, vt)) return hipErrorInvalidValue;
   ClipRecordPtrs full;
   if (!task_barrier_fill_records(a, rec, full)) return hipErrorInvalidValue;
-  return task_elastic_policy_launch(ElasticClippedVariablesLauncher{vt, full}, a, keep_task_outputs, cfg, stream, t);
+  return task_elastic_launch(ElasticClippedVariablesLauncher{vt, full}, a, keep_task_outputs, cfg, stream, t);
 }
 
 }  // namespace cbx

@@ -5,15 +5,15 @@
 // CDNA4 (gfx950).
 //
 // task_elastic_kernel (task_elastic_kernels.hip) with the rate lookup of
-// sma_optimise_variables_kernel: the shared text (task_elastic_policy_body.inc,
-// task_elastic_policy.h) behind the VariablesStep policy.  The tables are
+// sma_optimise_variables_kernel: the shared text (task_elastic_body.inc,
+// task_elastic_launch.h) behind the VariablesStep policy.  The tables are
 // kernel parameters of their own beside TaskBarrierArgs.
 //
 // One of the three compilation units of libcrossbow_sma_elastic_policies.so:
 // the device code of the other shared objects is not touched by it.
 #include <hip/hip_ext.h>
 
-#include "task_elastic_policy.h"
+#include "task_elastic_launch.h"
 
 namespace cbx {
 
@@ -28,7 +28,7 @@ __global__ __launch_bounds__(256) void task_elastic_variables_kernel(const TaskB
                                                                      const float *__restrict__ mult,
                                                                      const uint32_t nvars) {
   const typename step_policy<VariablesStep, R>::type step{chunks, bounds, mult, nvars};
-#include "task_elastic_policy_body.inc"
+#include "task_elastic_body.inc"
 }
 
 struct ElasticVariablesLauncher {
@@ -46,7 +46,7 @@ struct ElasticVariablesLauncher {
 hipError_t launch_task_elastic_variables(const TaskBarrierArgs &a, const VarTables &vt, bool keep_task_outputs,
                                          const LaunchConfig &cfg, hipStream_t stream, Timing t) {
   if (!task_barrier_tables_cover(a, vt)) return hipErrorInvalidValue;
-  return task_elastic_policy_launch(ElasticVariablesLauncher{vt}, a, keep_task_outputs, cfg, stream, t);
+  return task_elastic_launch(ElasticVariablesLauncher{vt}, a, keep_task_outputs, cfg, stream, t);
 }
 
 }  // namespace cbx

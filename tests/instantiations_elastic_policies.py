@@ -3,7 +3,7 @@
 The object holds three kernel families, one per step policy and compilation
 unit: ``task_elastic_variables_kernel``, ``task_elastic_clipped_kernel`` and
 ``task_elastic_clipped_variables_kernel`` (the three
-crossbow_amd/csrc/task_elastic_*_kernels.hip around task_elastic_policy_body.inc),
+crossbow_amd/csrc/task_elastic_*_kernels.hip around task_elastic_body.inc),
 behind the two doors ``cbx_step_and_synchronise_elastic_clipped_variables`` (the
 context, through ``TheGPU``, under update model 3 with ``set_elastic_average``)
 and ``cbx_ea_plan_step_and_optimise_clipped_variables`` (the seam, through
@@ -46,7 +46,7 @@ def per_variable(policy: str) -> bool:
 
 
 def expected_kernel(policy: str, case: Case, num_cus: int) -> str:
-    """launch_task_elastic_<policy> and the ladders above it (task_elastic_policy.h): te_form's, so the
+    """launch_task_elastic_<policy> and the ladders above it (task_elastic_launch.h): te_form's, so the
     template arguments are those of the plain kernel the same call would reach with both features off."""
     if policy not in POLICIES:
         raise ValueError(policy)

@@ -35,7 +35,7 @@ KERNEL = "task_elastic_kernel"
 
 
 def expected_kernel(case: Case, num_cus: int) -> str:
-    """launch_task_elastic and the ladders above it (task_elastic_kernels.hip)."""
+    """launch_task_elastic and the ladders above it (task_elastic_launch.h)."""
     if case.family != "task_barrier":
         raise ValueError(case.family)
     if case.base_mom or case.copy:

@@ -119,7 +119,7 @@ def test_the_kernels_are_a_shared_object_of_their_own_in_every_build():
     assert b"libcrossbow_sma_elastic_policies.so" in blob and b"$ORIGIN" in blob
     # the one staleness check covers the sources and the shared text
     deps = build._deps()
-    for name in SOURCES + ("task_elastic_policy.h", "task_elastic_policy_body.inc"):
+    for name in SOURCES + ("task_elastic_launch.h", "task_elastic_body.inc"):
         assert os.path.join(build.CSRC, name) in deps, name
     for script in ("scripts/build_sanitized.sh", "scripts/build_fake_rccl.sh", "__graft_entry__.py"):
         with open(os.path.join(ROOT, script)) as f:
