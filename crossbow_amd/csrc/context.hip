@@ -16,6 +16,7 @@
 //   * errors return codes; the JNI shim turns them back into exit(1).
 #include "context_internal.h"
 #include "optimise_plan.h"
+#include "task_ssgd_clipped_internal.h"
 #include "task_ssgd_internal.h"
 
 using namespace cbx::host;
@@ -1051,10 +1052,17 @@ int cbx_step_and_synchronise_elastic_clipped_variables(cbx_context *c, int first
 // and the receiving ones are two lists.  The same validation before the first
 // side effect; replica momentum, per-variable multipliers, s and copy flags play
 // no part, as in the two calls.  It ends as ssgd_step's unsplit form does.
-int cbx_step_and_synchronise_ssgd(cbx_context *c, int first, int clock, int autotune, const int *tasks,
-                                  void *const *streams, unsigned flags) {
-  const char *me = "cbx_step_and_synchronise_ssgd";
-  const char *instead = "cbx_replica_optimise and cbx_synchronise";
+// cbx_step_and_synchronise_ssgd (`clipped` false) refuses gradient clipping.
+// cbx_step_and_synchronise_ssgd_clipped honours it: with clipping on and a
+// stepping replica it runs the norm passes where the SMA call places them
+// (launch_fused_norms) and the kernel with the clipped step
+// (task_ssgd_clipped_kernels.hip); with clipping off, or nobody stepping, it is
+// the plain call's launch.
+static int step_and_synchronise_ssgd(cbx_context *c, int first, int clock, int autotune, const int *tasks,
+                                     void *const *streams, unsigned flags, bool clipped) {
+  const char *me = clipped ? "cbx_step_and_synchronise_ssgd_clipped" : "cbx_step_and_synchronise_ssgd";
+  const char *instead = clipped ? "cbx_replica_accumulate_clipped and cbx_synchronise"
+                                : "cbx_replica_optimise and cbx_synchronise";
   TraceRange trace(me);
   TRY(check_fused_call(c, me, first, tasks, flags, instead));
   const int size = c->size;
@@ -1066,7 +1074,8 @@ int cbx_step_and_synchronise_ssgd(cbx_context *c, int first, int clock, int auto
                 : type == CBX_UPDATE_SMA || type == CBX_UPDATE_SYNCHRONOUSEAMSGD
                     ? "the SMA barrier takes cbx_step_and_synchronise"
                     : "use cbx_replica_optimise and cbx_synchronise");
-  if (c->clip_on())
+  const bool clip = c->clip_on();
+  if (clip && !clipped)
     return fail(CBX_ERR_UNSUPPORTED, "%s: gradient clipping is on, and update model WORKER has no clipped step; turn it "
                 "off (cbx_set_gradient_clip) and use %s", me, instead);
   Device &d = c->devs[0];
@@ -1079,7 +1088,7 @@ int cbx_step_and_synchronise_ssgd(cbx_context *c, int first, int clock, int auto
     const SolverConf &conf = c->replicas[id]->conf;
     if (conf.momentumMethod == 1)  // synchronoussgd.cu:42-44, whatever the momentum
       return fail(CBX_ERR_UNSUPPORTED, "%s: replica %d: Nesterov's momentum has been disabled; %s refuses it too", me, id,
-                  "cbx_replica_optimise");
+                  clipped ? "cbx_replica_accumulate_clipped" : "cbx_replica_optimise");
     if (!ref) ref = &conf;
     if (conf.weightDecay != ref->weightDecay)
       return fail(CBX_ERR_UNSUPPORTED, "%s: replica %d steps with weight decay %g, an earlier one with %g; one launch "
@@ -1091,12 +1100,18 @@ int cbx_step_and_synchronise_ssgd(cbx_context *c, int first, int clock, int auto
   if (c->model.wpc <= 0) return fail(CBX_ERR_STATE, "S-SGD needs the work per clock (setModelWorkPerClock)");
   for (int id = 0; id < size; ++id)
     if (tasks[id] >= 0) TRY(check_rate_policy(c->replicas[id]->conf));
+  for (int id = 0; clip && id < size; ++id)
+    if (tasks[id] >= 0 && !c->replicas[id]->clip.dev)
+      return fail(CBX_ERR_STATE, "replica %d has no gradient-clip scratch", id);
 
   std::vector<float> lr((size_t)size, 0.0f);
   TRY(query_rates(c, tasks, lr));
 
   cbx::TaskSsgdArgs a;
   std::memset(&a, 0, sizeof(a));
+  cbx::ClipRecordPtrs records;  // of the stepping replicas, in their order
+  std::memset(&records, 0, sizeof(records));
+  std::vector<FusedNorm> norms;
   std::vector<hipStream_t> callers;
   for (int id : d.replicas) {  // increasing id order: the sequence's enqueue order, and common.c:208
     if (id < first || !c->locked[id]) continue;
@@ -1109,6 +1124,10 @@ int cbx_step_and_synchronise_ssgd(cbx_context *c, int first, int clock, int auto
     a.rate[k] = -lr[(size_t)id];  // synchronoussgd.cu:46
     hipStream_t st = streams && streams[id] ? reinterpret_cast<hipStream_t>(streams[id]) : d.stream;
     if (st != d.stream && std::find(callers.begin(), callers.end(), st) == callers.end()) callers.push_back(st);
+    if (clip) {
+      records.p[k] = r.clip.record();
+      norms.push_back({&r, st});
+    }
   }
   const bool mom = c->has_last && c->model.conf.momentum > 0;  // synchronoussgd.c:64 (base conf)
   a.z = reinterpret_cast<cbx::v4f *>(base_dev(c, d, CBX_BUF_DATA));
@@ -1120,6 +1139,8 @@ int cbx_step_and_synchronise_ssgd(cbx_context *c, int first, int clock, int auto
   a.momentum = mom ? c->model.conf.momentum : 0.0f;
 
   HIP_TRY(hipSetDevice(d.hip_id));
+  // the clipped call's norm passes, in front of the deferred waits
+  TRY(launch_fused_norms(c, d, norms));
   TRY(defer_caller_waits(c, d, callers));  // the launch comes after the gradients (synchronoussgd.cu:38-40)
   // as cbx_synchronise counts a barrier that is not SMA's: its start is a marker of its own (step_start_event)
   c->foreign_ops.fetch_add(1, std::memory_order_relaxed);
@@ -1127,10 +1148,22 @@ int cbx_step_and_synchronise_ssgd(cbx_context *c, int first, int clock, int auto
   cbx::LaunchConfig cfg = c->task_barrier_cfg;
   cfg.num_cus = d.num_cus;
   const bool keep = (flags & CBX_STEP_DISCARD_TASK_OUTPUTS) == 0;
-  HIP_TRY(cbx::launch_task_ssgd(a, keep, cfg, d.stream, {step_start_event(c, d, 0), step_stop_event(c, d, EV_A)}));
+  const cbx::Timing tm = {step_start_event(c, d, 0), step_stop_event(c, d, EV_A)};
+  if (norms.empty()) HIP_TRY(cbx::launch_task_ssgd(a, keep, cfg, d.stream, tm));
+  else HIP_TRY(cbx::launch_task_ssgd_clipped(a, records, keep, cfg, d.stream, tm));
   close_fused_step(c, d);  // the ring slot, cross_valid = false, last_step_split = false: ssgd_step's unsplit form
   TRY(finish_step(c));
   return finish_barrier(c, clock, autotune);
+}
+
+int cbx_step_and_synchronise_ssgd(cbx_context *c, int first, int clock, int autotune, const int *tasks,
+                                  void *const *streams, unsigned flags) {
+  return step_and_synchronise_ssgd(c, first, clock, autotune, tasks, streams, flags, false);
+}
+
+int cbx_step_and_synchronise_ssgd_clipped(cbx_context *c, int first, int clock, int autotune, const int *tasks,
+                                          void *const *streams, unsigned flags) {
+  return step_and_synchronise_ssgd(c, first, clock, autotune, tasks, streams, flags, true);
 }
 
 int cbx_unlock_any(cbx_context *c) {
@@ -1581,6 +1614,61 @@ static int ssgd_worker_step(cbx_context *c, Replica &r, Device &d, int task, hip
   return CBX_OK;
 }
 
+// ssgd_worker_step with gradient clipping on: the norm pass where sma_task_step
+// places it (on the task's stream, behind the last barrier's use of the replica
+// and the replica's own last step), then the clipped step on the sync stream
+// (task_ssgd_clipped_kernels.hip), which on the record's skip bit touches
+// nothing.  Everything is refused before the rate query.
+static int ssgd_worker_step_clipped(cbx_context *c, Replica &r, Device &d, int task, hipStream_t st) {
+  SolverConf &conf = r.conf;
+  if (conf.momentumMethod == 1) return fail(CBX_ERR_UNSUPPORTED, "Nesterov's momentum has been disabled");  // :42-44
+  if (!r.clip.dev) return fail(CBX_ERR_STATE, "replica %d has no gradient-clip scratch", r.id);
+  float lr = 0.0f;
+  TRY(conf.learning_rate(task, &lr));  // may raise _copy (solverconfiguration.c:133,147)
+  cbx::SsgdArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.wsrc = reinterpret_cast<const cbx::v4f *>(replica_dev(d, r, CBX_BUF_DATA));
+  a.g = reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_GRADIENT));
+  a.acc = reinterpret_cast<cbx::v4f *>(base_dev(c, d, CBX_BUF_GRADIENT));
+  a.n4 = c->n4;
+  a.rate = -lr;  // :46
+  a.wd = conf.weightDecay;
+  HIP_TRY(hipSetDevice(d.hip_id));
+  if (st == d.stream) TRY(flush_task_waits(c));  // in order after updates made on other streams
+  if (st != d.stream) {
+    // The record and g must not be written while the last barrier, or this
+    // replica's last step on the sync stream, still reads them.
+    if (d.step_event) HIP_TRY(hipStreamWaitEvent(st, d.step_event, 0));
+    if (r.client) HIP_TRY(hipStreamWaitEvent(st, r.client, 0));
+  }
+  HIP_TRY(cbx::launch_gradient_norm(reinterpret_cast<const float *>(a.g), c->n, r.clip, c->clip_max_norm,
+                                    c->clip_skip_nonfinite, c->clip_norm_policy, st));
+  if (st != d.stream) {
+    // :38-40: the sync stream waits for the task's gradient, and now its record.
+    if (!r.client) HIP_TRY(hipEventCreateWithFlags(&r.client, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(r.client, st));
+    HIP_TRY(hipStreamWaitEvent(d.stream, r.client, 0));
+  }
+  cbx::LaunchConfig cfg = c->aux_cfg;
+  cfg.num_cus = d.num_cus;
+  cfg.blocks_per_cu = 0;
+  HIP_TRY(cbx::launch_ssgd_accumulate_clipped(a, r.clip.record(), cfg, d.stream, {}));
+  if (st != d.stream) HIP_TRY(hipEventRecord(r.client, d.stream));  // the end of this step, for the replica's next
+  return CBX_OK;
+}
+
+static int replica_accumulate_clipped_impl(cbx_context *c, int id, int task, void *stream) {
+  TRY(check_replica(c, id, true));
+  Replica &r = *c->replicas[id];
+  Device &d = c->devs[r.local];
+  if (c->model.type != CBX_UPDATE_WORKER)
+    return fail(CBX_ERR_UNSUPPORTED, "cbx_replica_accumulate_clipped: update model %d; it is the task step of WORKER (1) "
+                "only, the other models take cbx_replica_optimise", c->model.type);
+  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : d.stream;
+  if (!c->clip_on()) return ssgd_worker_step(c, r, d, task, st);  // cbx_replica_optimise: the same kernel
+  return ssgd_worker_step_clipped(c, r, d, task, st);
+}
+
 static int replica_optimise_impl(cbx_context *c, int id, int task, void *stream);
 static int replica_optimise_variables_impl(cbx_context *c, int id, int task, int op, void *stream);
 
@@ -1592,6 +1680,14 @@ static int replica_optimise_variables_impl(cbx_context *c, int id, int task, int
 int cbx_replica_optimise(cbx_context *c, int id, int task, void *stream) {
   TraceRange trace("cbx_replica_optimise");
   const int rc = replica_optimise_impl(c, id, task, stream);
+  if (c) c->foreign_ops.fetch_add(1, std::memory_order_release);
+  return rc;
+}
+
+// The foreign-op counter as in cbx_replica_optimise.
+int cbx_replica_accumulate_clipped(cbx_context *c, int id, int task, void *stream) {
+  TraceRange trace("cbx_replica_accumulate_clipped");
+  const int rc = replica_accumulate_clipped_impl(c, id, task, stream);
   if (c) c->foreign_ops.fetch_add(1, std::memory_order_release);
   return rc;
 }

@@ -33,6 +33,7 @@
 // which they are enqueued, its diagrams, and the bucket geometry.
 #include "context_internal.h"
 #include "optimise_plan.h"
+#include "task_ssgd_clipped_internal.h"
 #include "task_ssgd_internal.h"
 
 using namespace cbx::host;
@@ -882,13 +883,23 @@ int cbx_ssgd_plan_step(cbx_sma_plan *p, void *const *streams, float *const *z, f
 // loop, the elements past it the kernel's TAIL workgroups
 // (task_ssgd_kernels.hip).  Everything is validated before the launch; the plan
 // queues no wait of its own.
-int cbx_ssgd_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *const *z, float *const *last,
-                                    float *const *acc, int nreplicas, const int *replica_device, float *const *w,
-                                    float *const *g, const int *locked, const int *step, const float *learning_rate,
-                                    float momentum, float weight_decay, int wpc, int first, unsigned flags) {
-  const char *me = "cbx_ssgd_plan_step_and_optimise";
+// cbx_ssgd_plan_step_and_optimise_clipped (`clipped`) is the same call with
+// every stepping replica's norm pass over its slot's scratch on streams[0], in
+// id order, in front of the launch, and the clipped step inside it
+// (task_ssgd_clipped_kernels.hip): the slot rules are SeamClipped's.  When
+// nobody steps it is the plain call's launch.
+static int ssgd_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *const *z, float *const *last,
+                                       float *const *acc, int nreplicas, const int *replica_device, float *const *w,
+                                       float *const *g, const int *locked, const int *step,
+                                       const float *learning_rate, float momentum, float weight_decay, int wpc,
+                                       int first, unsigned flags, bool clipped, const SeamClip &clip = SeamClip()) {
+  const char *me = clipped ? "cbx_ssgd_plan_step_and_optimise_clipped" : "cbx_ssgd_plan_step_and_optimise";
   TraceRange trace(me);
   if (!p) return fail(CBX_ERR_INVALID, "null plan");
+  if (clipped && (!(clip.max_norm >= 0.0f) || std::isinf(clip.max_norm)))
+    return fail(CBX_ERR_INVALID, "%s: max_norm %g is negative, NaN or infinite", me, (double)clip.max_norm);
+  if (clipped && clip.skip_nonfinite != 0 && clip.skip_nonfinite != 1)
+    return fail(CBX_ERR_INVALID, "%s: skip_nonfinite %d is neither 0 nor 1", me, clip.skip_nonfinite);
   if (!streams || !z || !acc || nreplicas < 0 || (nreplicas > 0 && (!replica_device || !w || !locked || !step)))
     return fail(CBX_ERR_INVALID, "%s: missing arguments", me);
   if (flags & ~CBX_STEP_DISCARD_TASK_OUTPUTS) return fail(CBX_ERR_INVALID, "%s: unknown flag bits 0x%x", me, flags);
@@ -912,6 +923,8 @@ int cbx_ssgd_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float
   cbx::TaskSsgdArgs a;
   std::memset(&a, 0, sizeof(a));
   int participating = 0;
+  int slot_of[cbx::kMaxReplicas];  // clipped: the slot of stepping replica k
+  uint64_t slots_taken = 0;
   for (int id = first; id < nreplicas; ++id) {  // increasing id order: the steps' enqueue order, and common.c:208
     if (!locked[id]) continue;
     if (replica_device[id] != 0) return fail(CBX_ERR_INVALID, "%s: replica %d on device %d of 1", me, id, replica_device[id]);
@@ -920,10 +933,15 @@ int cbx_ssgd_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float
     // a replica that only joins is one write stream: its g may be NULL
     if (st && (!g[id] || !aligned16(g[id])))
       return fail(CBX_ERR_INVALID, "%s: stepping replica %d: g must be non-null and 16-byte aligned", me, id);
+    if (clipped && st) {
+      if (!clip.slot) return fail(CBX_ERR_INVALID, "%s: stepping replica %d without a slot list", me, id);
+      TRY(take_clip_slot(me, id, clip.slot[id], &slots_taken));
+    }
     if (++participating > cbx::kMaxReplicas) continue;  // counted on, refused below
     a.w[a.nrecv++] = reinterpret_cast<cbx::v4f *>(w[id]);
     if (!st) continue;
     const int k = a.nstep++;
+    slot_of[k] = clipped ? clip.slot[id] : -1;
     a.sw[k] = reinterpret_cast<const cbx::v4f *>(w[id]);
     a.g[k] = reinterpret_cast<cbx::v4f *>(g[id]);
     a.rate[k] = -1.0f * learning_rate[id];  // synchronoussgd.cu:46
@@ -944,8 +962,47 @@ int cbx_ssgd_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float
   HIP_TRY(hipSetDevice(d.hip_id));
   cbx::LaunchConfig cfg = p->task_barrier_cfg;
   cfg.num_cus = d.num_cus;
-  HIP_TRY(cbx::launch_task_ssgd(a, keep, cfg, static_cast<hipStream_t>(streams[0]), p->next_timing()));
+  hipStream_t st0 = static_cast<hipStream_t>(streams[0]);
+  if (!clipped || a.nstep == 0) {  // nobody steps: nothing to clip
+    HIP_TRY(cbx::launch_task_ssgd(a, keep, cfg, st0, p->next_timing()));
+    return CBX_OK;
+  }
+  // The norm passes as cbx_ssgd_plan_accumulate_clipped runs them: the records
+  // are the sequence's bits.  Every scratch before the first launch: a failed
+  // allocation bumps no counter.
+  cbx::ClipRecordPtrs records;
+  std::memset(&records, 0, sizeof(records));
+  cbx::ClipScratch *cs[cbx::kMaxReplicas] = {};
+  for (int k = 0; k < a.nstep; ++k) TRY(clip_slot(p, me, 0, slot_of[k], &cs[k]));
+  for (int k = 0; k < a.nstep; ++k) {
+    HIP_TRY(cbx::launch_gradient_norm(reinterpret_cast<const float *>(a.g[k]), p->n, *cs[k], clip.max_norm,
+                                      clip.skip_nonfinite == 1, p->clip_norm_policy, st0));
+    records.p[k] = cs[k]->record();
+  }
+  HIP_TRY(cbx::launch_task_ssgd_clipped(a, records, keep, cfg, st0, p->next_timing()));
   return CBX_OK;
+}
+
+int cbx_ssgd_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *const *z, float *const *last,
+                                    float *const *acc, int nreplicas, const int *replica_device, float *const *w,
+                                    float *const *g, const int *locked, const int *step, const float *learning_rate,
+                                    float momentum, float weight_decay, int wpc, int first, unsigned flags) {
+  return ssgd_plan_step_and_optimise(p, streams, z, last, acc, nreplicas, replica_device, w, g, locked, step,
+                                     learning_rate, momentum, weight_decay, wpc, first, flags, false);
+}
+
+int cbx_ssgd_plan_step_and_optimise_clipped(cbx_sma_plan *p, void *const *streams, float *const *z,
+                                            float *const *last, float *const *acc, int nreplicas,
+                                            const int *replica_device, float *const *w, float *const *g,
+                                            const int *locked, const int *step, const float *learning_rate,
+                                            const int *slot, float max_norm, int skip_nonfinite, float momentum,
+                                            float weight_decay, int wpc, int first, unsigned flags) {
+  SeamClip clip;
+  clip.slot = slot;
+  clip.max_norm = max_norm;
+  clip.skip_nonfinite = skip_nonfinite;
+  return ssgd_plan_step_and_optimise(p, streams, z, last, acc, nreplicas, replica_device, w, g, locked, step,
+                                     learning_rate, momentum, weight_decay, wpc, first, flags, true, clip);
 }
 
 // crossbowKernelOptimiserSynchronousSGD (kernels/optimisers/synchronoussgd.cu:
@@ -1188,6 +1245,43 @@ int cbx_sma_plan_optimise_clipped(cbx_sma_plan *p, int k, int slot, void *stream
   a.tail_lo = a.n4 * 4;  // the elements past the last whole trip ride the same launch
   a.tail_hi = p->n;
   HIP_TRY(cbx::launch_sma_optimise_clipped(a, cs->record(), cfg, st));
+  return CBX_OK;
+}
+
+// cbx_ssgd_accumulate_buffers with the slot's record: the norm pass and the
+// reduce on `stream`, then the clipped step behind them
+// (task_ssgd_clipped_kernels.hip), which on the skip bit touches nothing.
+int cbx_ssgd_plan_accumulate_clipped(cbx_sma_plan *p, int k, int slot, void *stream, const float *w, float *g,
+                                     float *acc, float learning_rate, float weight_decay, float max_norm,
+                                     int skip_nonfinite) {
+  const char *me = "cbx_ssgd_plan_accumulate_clipped";
+  TraceRange trace(me);
+  if (!p) return fail(CBX_ERR_INVALID, "null plan");
+  if (!(max_norm >= 0.0f) || std::isinf(max_norm))
+    return fail(CBX_ERR_INVALID, "%s: max_norm %g is negative, NaN or infinite", me, (double)max_norm);
+  if (skip_nonfinite != 0 && skip_nonfinite != 1)
+    return fail(CBX_ERR_INVALID, "%s: skip_nonfinite %d is neither 0 nor 1", me, skip_nonfinite);
+  if (!g || !acc || (weight_decay > 0.0f && !w)) return fail(CBX_ERR_INVALID, "%s: missing buffers", me);
+  if (!aligned16(g) || !aligned16(acc) || (weight_decay > 0.0f && !aligned16(w)))
+    return fail(CBX_ERR_INVALID, "%s: buffers must be 16-byte aligned", me);
+  cbx::ClipScratch *cs = nullptr;
+  TRY(clip_slot(p, me, k, slot, &cs));
+  auto &d = p->devs[k];
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  cbx::SsgdArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.wsrc = reinterpret_cast<const cbx::v4f *>(w);
+  a.g = reinterpret_cast<cbx::v4f *>(g);
+  a.acc = reinterpret_cast<cbx::v4f *>(acc);
+  a.n4 = p->n4b;
+  a.rate = -1.0f * learning_rate;  // synchronoussgd.cu:46
+  a.wd = weight_decay;
+  a.tail_lo = a.n4 * 4;  // the elements past the last whole trip ride the same launch
+  a.tail_hi = p->n;
+  cbx::LaunchConfig cfg = cbx::aux_launch_config();
+  cfg.num_cus = d.num_cus;
+  HIP_TRY(cbx::launch_gradient_norm(g, p->n, *cs, max_norm, skip_nonfinite == 1, p->clip_norm_policy, st));
+  HIP_TRY(cbx::launch_ssgd_accumulate_clipped(a, cs->record(), cfg, st));
   return CBX_OK;
 }
 

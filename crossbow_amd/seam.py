@@ -171,6 +171,41 @@ class SmaPlan:
             ctypes.c_float(momentum), ctypes.c_float(weight_decay), wpc, first, ctypes.c_uint(flags)),
             "cbx_ssgd_plan_step_and_optimise")
 
+    def ssgd_accumulate_clipped(self, k: int, slot: int, stream: int, w: Optional[int], g: int, acc: int,
+                                learning_rate: float, weight_decay: float, max_norm: float,
+                                skip_nonfinite: bool = False) -> None:
+        """``cbx_ssgd_plan_accumulate_clipped``: one task's synchronous-SGD step
+        with gradient clipping by global L2 norm (``max_norm``; 0: none) and
+        the non-finite skip, on plan device ``k``; asynchronous on ``stream``.
+        ``slot`` in [0, 64) names the plan-owned record and slab.  A skipped
+        gradient leaves ``g`` and ``acc`` alone."""
+        _raise(self.lib, self.lib.cbx_ssgd_plan_accumulate_clipped(
+            self._p, k, slot, stream or None, w or None, g, acc, ctypes.c_float(learning_rate),
+            ctypes.c_float(weight_decay), ctypes.c_float(max_norm), 1 if skip_nonfinite else 0),
+            "cbx_ssgd_plan_accumulate_clipped")
+
+    def ssgd_step_and_optimise_clipped(self, streams: Sequence[int], z: Sequence[int],
+                                       last: Optional[Sequence[Optional[int]]], acc: Sequence[int],
+                                       replicas: Sequence[Tuple[int, int, Optional[int], int, int, float]],
+                                       momentum: float, weight_decay: float, wpc: int, first: int = 0, flags: int = 0,
+                                       slots: Optional[Sequence[int]] = None, max_norm: float = 0.0,
+                                       skip_nonfinite: bool = False) -> None:
+        """``ssgd_step_and_optimise`` with the clipped step of
+        ``ssgd_accumulate_clipped`` (``cbx_ssgd_plan_step_and_optimise_clipped``):
+        stepping replica id is clipped to ``max_norm`` (0: none) through the
+        record of ``slots[id]``, whose norm pass the call runs on ``streams[0]``
+        first, and adds nothing when ``skip_nonfinite`` and its gradient holds
+        a NaN or an infinity.  Two stepping replicas take two slots.  Otherwise
+        the same arguments."""
+        rate = (ctypes.c_float * max(1, len(replicas)))(*[float(r[5]) for r in replicas])
+        _raise(self.lib, self.lib.cbx_ssgd_plan_step_and_optimise_clipped(
+            self._p, _ptrs(streams), _ptrs(z), _ptrs(last) if last is not None else None, _ptrs(acc),
+            len(replicas), _ints([r[0] for r in replicas]), _ptrs([r[1] for r in replicas]),
+            _ptrs([r[2] for r in replicas]), _ints([r[3] for r in replicas]), _ints([r[4] for r in replicas]), rate,
+            _ints(slots) if slots is not None else None, ctypes.c_float(max_norm), 1 if skip_nonfinite else 0,
+            ctypes.c_float(momentum), ctypes.c_float(weight_decay), wpc, first, ctypes.c_uint(flags)),
+            "cbx_ssgd_plan_step_and_optimise_clipped")
+
     def elastic_step(self, streams: Sequence[int], z: Sequence[int],
                      replicas: Sequence[Tuple[int, int, Optional[int], int]], alpha: float, first: int = 0) -> None:
         """One elastic-averaging barrier (``cbx_ea_plan_step``).  ``replicas[id]``

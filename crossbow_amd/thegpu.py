@@ -278,6 +278,17 @@ class TheGPU:
         return self._step_and_synchronise(self._L.cbx_step_and_synchronise_ssgd, first, clock, autotune, tasks,
                                           streams, flags)
 
+    def step_and_synchronise_ssgd_clipped(self, first: int, clock: int, autotune: int, tasks: Sequence[int],
+                                          streams: Optional[Sequence[Optional[int]]] = None, flags: int = 0) -> int:
+        """``cbx_step_and_synchronise_ssgd_clipped``:
+        ``step_and_synchronise_ssgd`` with gradient clipping on
+        (``set_gradient_clip``), which that call refuses: each stepping
+        replica's norm pass runs in front of the launch, and a replica whose
+        gradient is skipped adds nothing to the base gradient.  Same arguments;
+        with clipping off it is that call."""
+        return self._step_and_synchronise(self._L.cbx_step_and_synchronise_ssgd_clipped, first, clock, autotune,
+                                          tasks, streams, flags)
+
     def _step_and_synchronise(self, fn, first, clock, autotune, tasks, streams, flags) -> int:
         tasks = list(tasks)
         N = self.num_replicas()
@@ -410,6 +421,14 @@ class TheGPU:
         None enqueues on the replica device's synchronisation stream.
         """
         check(self._L.cbx_replica_optimise(self._ctx, id, task, ctypes.c_void_p(stream) if stream else None))
+
+    def replica_accumulate_clipped(self, id: int, task: int, stream: Optional[int] = None) -> None:
+        """``cbx_replica_accumulate_clipped``: the synchronous-SGD task step
+        (update model WORKER) with gradient clipping on: the replica's norm
+        pass on ``stream``, then the clipped step on the synchronisation
+        stream, which a skipped gradient leaves without a trace.  With clipping
+        off it is ``replica_optimise``."""
+        check(self._L.cbx_replica_accumulate_clipped(self._ctx, id, task, ctypes.c_void_p(stream) if stream else None))
 
     def replica_optimise_variables(self, id: int, task: int, op: int, stream: Optional[int] = None) -> None:
         """crossbowStreamSynchronousEamsgdModelUpdate (stream.c:422-479): the

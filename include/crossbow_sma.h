@@ -521,6 +521,64 @@ int cbx_step_and_synchronise_elastic_clipped_variables (cbx_context *ctx, int fi
  * The launch shape is cbx_set_task_barrier_kernel_config's.                 */
 int cbx_step_and_synchronise_ssgd (cbx_context *ctx, int first, int clock, int autotune,
                                    const int *tasks, void *const *streams, unsigned flags);
+/* cbx_step_and_synchronise_ssgd with gradient clipping (cbx_set_gradient_clip),
+ * which that call refuses.  Under S-SGD every replica's gradient goes into one
+ * accumulator whose result is broadcast to every replica: one replica's NaN or
+ * exploding gradient would reach the base model and all R replicas in one
+ * barrier.  Same parameters.  Clipping is per replica, by the norm of that
+ * replica's own g, as everywhere.
+ *
+ * The call runs every stepping replica's norm pass and reduce where
+ * cbx_replica_accumulate_clipped runs them (on streams[id], behind the last
+ * barrier's use of the replica, in front of the launch) and then one launch.
+ * Per element, for stepping replica i in ASCENDING ID ORDER with the record
+ * (S, K, scale_i, flags_i) its reduce left:
+ *   skip bit set:  replica i contributes nothing: acc is not touched by it (no
+ *                  fma, not even with 0), g_i is neither read nor written by the
+ *                  step, w_i is not read
+ *   otherwise:     gv = scale_i * g_i          one fp32 multiply, before weight decay
+ *                  gv = fma (wd, w_i, gv)      (wd > 0)
+ *                  g_i = gv                    (outputs kept: always written with
+ *                                               clipping on, as the SMA clipped
+ *                                               step leaves g)
+ *                  acc = fma (rate_i, gv, acc)
+ * and everything after the accumulator as in cbx_step_and_synchronise_ssgd:
+ * D = ratio * acc, the base momentum, z, base gradient = +0, w_j = z for every
+ * participating replica, stepping, skipped or only joining.  ratio stays
+ * (float) (1.0 / (double) (float) wpc) WHATEVER WAS SKIPPED: a skipped replica
+ * is a zero in the mean, the mean is not taken over the replicas that are left.
+ * Skipped wins over clipped.  The records and their counts (steps,
+ * clipped_steps, skipped_steps; cbx_replica_clip_stats) are what the norm pass
+ * writes in every other clipped call.
+ *
+ * The contract.  With flags == 0 every buffer, every record and every piece of
+ * host state is left bit for bit as after, on one device,
+ *   cbx_replica_accumulate_clipped (ctx, id, tasks[id], streams[id])  for every
+ *                               id with tasks[id] >= 0, in ascending id order,
+ *   cbx_synchronise (ctx, first, clock, autotune, 0).
+ * With CBX_STEP_DISCARD_TASK_OUTPUTS, g_i of the stepping replicas is not
+ * written, with or without weight decay.  With clipping off, or with nobody
+ * stepping, the call is cbx_step_and_synchronise_ssgd: the same kernel, the
+ * same bits, no norm pass.
+ *
+ * Bytes per element, R replicas stepping and receiving, base momentum on, none
+ * skipped (each skipped replica moves 4 to 12 fewer):
+ *   no weight decay, g kept        (12R + 24) n
+ *   no weight decay, g discarded   ( 8R + 24) n
+ *   weight decay, g kept           (16R + 24) n
+ *   weight decay, g discarded      (12R + 24) n
+ *   the norm passes, in every form  + 4R n
+ * against the sequence's (16R + 4R + 24) n = (20R + 24) n without weight decay
+ * and (24R + 24) n with it, norm passes included ((16R + 24) n and (20R + 24) n
+ * of steps and barrier beside the same 4R n).
+ *
+ * Everything is checked before the first side effect, in
+ * cbx_step_and_synchronise_ssgd's order with its codes, except that clipping is
+ * honoured; then CBX_ERR_STATE for a stepping replica without clip scratch.
+ * A refused call launches no norm pass and changes no buffer, flag, clock or
+ * record.                                                                   */
+int cbx_step_and_synchronise_ssgd_clipped (cbx_context *ctx, int first, int clock, int autotune,
+                                           const int *tasks, void *const *streams, unsigned flags);
 /* TheGPU.unlockAny() GPU.c:1142-1149 -> modelmanager.c:233-245           */
 int cbx_unlock_any (cbx_context *ctx);
 
@@ -697,6 +755,23 @@ int cbx_replica_set_disabled (cbx_context *ctx, int id, int flag);
  * and a multiplier other than 1 registered, every variable steps with its
  * own rate: see there.                                                     */
 int cbx_replica_optimise (cbx_context *ctx, int id, int task, void *stream);
+/* The WORKER task step with gradient clipping on (cbx_set_gradient_clip), which
+ * cbx_replica_optimise refuses.  The host side is cbx_replica_optimise's under
+ * WORKER: the rate query (which may raise the copy flag), the refusal of
+ * Nesterov momentum, the sync stream's wait for `stream`.  The norm pass and its
+ * reduce run on `stream` (NULL: the sync stream) where cbx_replica_optimise
+ * places them for SMA, behind the last barrier's use of the replica and this
+ * replica's last step; the clipped step then runs on the sync stream, where the
+ * plain step runs.  With the record's skip bit the step returns having touched
+ * nothing: g, w and the base gradient keep every bit.  Otherwise
+ *   g = scale * g, one fp32 multiply before weight decay; g = fma (wd, w, g);
+ *   g written, always;  base gradient = fma (rate, g, base gradient).
+ * (16 n bytes, 20 n with weight decay, beside the norm pass's 4 n.)  With
+ * clipping off it is cbx_replica_optimise: the same kernel, the same bits.
+ * CBX_ERR_UNSUPPORTED under any update model other than WORKER and for
+ * Nesterov momentum; CBX_ERR_STATE for a replica without clip scratch; both
+ * before the rate query.                                                    */
+int cbx_replica_accumulate_clipped (cbx_context *ctx, int id, int task, void *stream);
 /* The per-operator step, crossbowStreamSynchronousEamsgdModelUpdate
  * (stream.c:422-479): cbx_replica_optimise's step on the variables
  * registered under operator `op` only (orders 1..count), so that the update
@@ -1424,6 +1499,42 @@ int cbx_ssgd_plan_step_and_optimise (cbx_sma_plan *plan, void *const *streams, f
                                      float *const *w, float *const *g, const int *locked, const int *step,
                                      const float *learning_rate, float momentum, float weight_decay,
                                      int wpc, int first, unsigned flags);
+/* The same pair with gradient clipping, over the caller's buffers of exactly
+ * `elements` floats: what cbx_replica_accumulate_clipped and
+ * cbx_step_and_synchronise_ssgd_clipped are to a context.
+ *
+ * cbx_ssgd_plan_accumulate_clipped is cbx_ssgd_accumulate_buffers on plan
+ * device k with the record of `slot` (cbx_sma_plan_optimise_clipped's slots):
+ * the norm pass and the reduce over g on `stream`, then the clipped step behind
+ * them.  A skipped gradient leaves g and acc alone; otherwise g = scale * g
+ * before weight decay, g is written always, acc = fma (-learning_rate, g, acc).
+ * w may be NULL when weight_decay == 0.  cbx_sma_plan_clip_stats reads the
+ * record.
+ *
+ * cbx_ssgd_plan_step_and_optimise_clipped is cbx_ssgd_plan_step_and_optimise
+ * plus slot, max_norm and skip_nonfinite: slot[id] names stepping replica id's
+ * record, under the rules of cbx_sma_plan_step_and_optimise_clipped
+ * (CBX_ERR_INVALID, before any launch, for a stepping replica without a slot
+ * list, a slot out of [0, 64), two stepping replicas sharing a slot, a max_norm
+ * that is negative, NaN or infinite, a skip_nonfinite other than 0 or 1).  The
+ * norm passes run on streams[0] in id order in front of the launch, the last
+ * elements ride the same launch.  The arithmetic and the byte counts are
+ * cbx_step_and_synchronise_ssgd_clipped's: a skipped replica adds nothing, and
+ * the mean is still taken over wpc.  With flags == 0 every buffer and record is
+ * left bit for bit as after cbx_ssgd_plan_accumulate_clipped (plan, 0,
+ * slot[id], streams[0], w[id], g[id], acc[0], learning_rate[id], weight_decay,
+ * max_norm, skip_nonfinite) for every stepping id in id order, then
+ * cbx_ssgd_plan_step.  With CBX_STEP_DISCARD_TASK_OUTPUTS g[id] is not written.
+ * When nobody steps it is cbx_ssgd_plan_step_and_optimise's launch.         */
+int cbx_ssgd_plan_accumulate_clipped (cbx_sma_plan *plan, int k, int slot, void *stream, const float *w, float *g,
+                                      float *acc, float learning_rate, float weight_decay, float max_norm,
+                                      int skip_nonfinite);
+int cbx_ssgd_plan_step_and_optimise_clipped (cbx_sma_plan *plan, void *const *streams, float *const *z,
+                                             float *const *last, float *const *acc, int nreplicas,
+                                             const int *replica_device, float *const *w, float *const *g,
+                                             const int *locked, const int *step, const float *learning_rate,
+                                             const int *slot, float max_norm, int skip_nonfinite, float momentum,
+                                             float weight_decay, int wpc, int first, unsigned flags);
 /* The same seam for the two averaging barriers, over an existing plan: they
  * share its acc / D scratch, communicators, comm stream, per-bucket events
  * and cbx_sma_plan_set_buckets with the SMA and S-SGD steps, so any sequence
