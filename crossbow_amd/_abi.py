@@ -79,6 +79,18 @@ class ClipStats(_c.Structure):
 CLIP_CLIPPED, CLIP_SKIPPED = 1, 2  # cbx_clip_stats.flags
 _CS = _c.POINTER(ClipStats)
 
+
+class AdaptiveStats(_c.Structure):
+    """``cbx_adaptive_stats``: 32 bytes, no implicit padding."""
+    _fields_ = [("w_sq", _c.c_double), ("g_sq", _c.c_double), ("nonfinite", _c.c_ulonglong),
+                ("trust", _c.c_float), ("flags", _c.c_uint)]
+
+
+# The same layout as a numpy structured dtype (what replica_adaptive_stats returns).
+ADAPTIVE_STATS_FIELDS = [("w_sq", "<f8"), ("g_sq", "<f8"), ("nonfinite", "<u8"), ("trust", "<f4"), ("flags", "<u4")]
+ADAPTIVE_APPLIED, ADAPTIVE_EXCLUDED, ADAPTIVE_DEGENERATE, ADAPTIVE_CAPPED = 1, 2, 4, 8  # cbx_adaptive_stats.flags
+_AS = _c.POINTER(AdaptiveStats)
+
 # name -> (restype, argtypes); mirrors include/crossbow_sma.h one to one.
 SIGNATURES = {
     "cbx_abi_version": (_I, []),
@@ -142,6 +154,10 @@ SIGNATURES = {
     "cbx_replica_optimise_variables": (_I, [_P, _I, _I, _I, _P]),
     "cbx_set_gradient_clip": (_I, [_P, _F, _I]),
     "cbx_replica_clip_stats": (_I, [_P, _I, _CS]),
+    "cbx_set_adaptive_rate": (_I, [_P, _F, _F, _I]),
+    "cbx_set_adaptive_kernel_policy": (_I, [_P, _I]),
+    "cbx_set_model_variable_adaptive_rate": (_I, [_P, _I, _I, _I]),
+    "cbx_replica_adaptive_stats": (_I, [_P, _I, _AS, _I]),
     "cbx_replica_get_copy": (_I, [_P, _I]),
     "cbx_replica_set_copy": (_I, [_P, _I, _I]),
     "cbx_acquire_access": (_I, [_P, _IP]),
@@ -215,6 +231,11 @@ SIGNATURES = {
     "cbx_sma_plan_optimise_variables": (_I, [_P, _I, _P, _P, _P, _P, _P, _F, _F, _F, _I, _I]),
     "cbx_sma_plan_optimise_clipped": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _I, _I]),
     "cbx_sma_plan_clip_stats": (_I, [_P, _I, _I, _P, _CS]),
+    "cbx_sma_plan_set_adaptive": (_I, [_P, _UB, _I]),
+    "cbx_sma_plan_optimise_adaptive": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _I]),
+    "cbx_sma_plan_adaptive_stats": (_I, [_P, _I, _I, _P, _AS, _I]),
+    "cbx_sma_plan_optimise_adaptive_timed": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _I, _FP, _FP,
+                                                  _FP]),
     "cbx_sma_plan_gradient_norm": (_I, [_P, _I, _I, _P, _P, _F, _I, _I, _FP, _FP]),
     "cbx_sma_plan_average_batchnorm": (_I, [_P, _I, _IP, _PP, _PP, _IP]),
     "cbx_ssgd_plan_step": (_I, [_P, _PP, _PP, _PP, _PP, _I, _IP, _PP, _IP, _F, _I, _I]),

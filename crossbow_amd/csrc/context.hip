@@ -205,6 +205,10 @@ int cbx_free(cbx_context *c) {
       (void)hipSetDevice(c->devs[r->local].hip_id);
       cbx::clip_scratch_free(r->clip);
     }
+    if (r && r->adaptive.dev && r->local >= 0) {
+      (void)hipSetDevice(c->devs[r->local].hip_id);
+      cbx::adaptive_scratch_free(r->adaptive);
+    }
   }
   for (std::vector<Replica *> *list : {&c->replicas, &c->retired})
     for (Replica *r : *list) {
@@ -300,6 +304,29 @@ int cbx_set_model_variable_learning_rate_multiplier(cbx_context *c, int id, int 
         HIP_TRY(hipMemcpy(d.var_tables.mult + v, &multiplier, sizeof(float), hipMemcpyHostToDevice));
         if (d.var_tables_padded.mult)
           HIP_TRY(hipMemcpy(d.var_tables_padded.mult + v, &multiplier, sizeof(float), hipMemcpyHostToDevice));
+      }
+    }
+  }
+  return CBX_OK;
+}
+
+int cbx_set_model_variable_adaptive_rate(cbx_context *c, int id, int order, int enable) {
+  TRY(check_ctx(c));
+  auto it = c->model.vars.find({id, order});
+  if (it == c->model.vars.end()) return fail(CBX_ERR_INVALID, "model variable not found (id %d, order %d)", id, order);
+  if (enable != 0 && enable != 1)
+    return fail(CBX_ERR_INVALID, "cbx_set_model_variable_adaptive_rate: %d is neither 0 nor 1", enable);
+  it->second.adaptive = enable == 1;
+  if (c->manager && !c->var_bounds.empty()) {
+    // After cbx_set_model_manager: a blocking update, every device drained
+    // first, as for the multipliers above.
+    const int v = variable_index(c, id, order);
+    if (v >= 0) {
+      for (Device &d : c->devs) {
+        if (!d.adaptive_tables.dev) continue;
+        HIP_TRY(hipSetDevice(d.hip_id));
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(cbx::adaptive_tables_set_enable(d.adaptive_tables, (uint32_t)v, enable == 1));
       }
     }
   }
@@ -463,6 +490,14 @@ static int build_variable_tables(cbx_context *c) {
   const bool have_padded = cbx::build_padded_optimise_plan(elems.data(), (int)V, c->n, c->n4 * 4, &padded);
   std::vector<float> padded_mult(c->var_mult);
   padded_mult.push_back(1.0f);
+  // The piece table of the adaptive step's reduction (cbx_set_adaptive_rate),
+  // beside the tables of the per-variable step; every local replica gets its
+  // records, trust table and slab, all zeros.
+  cbx::StatsPlan pieces;
+  if (!cbx::build_stats_plan(elems.data(), (int)V, c->n, &pieces))
+    return fail(CBX_ERR_INVALID, "the variables of the model do not sum to its %lld elements", (long long)c->n);
+  std::vector<unsigned char> adaptive(V);
+  for (size_t v = 0; v < V; ++v) adaptive[v] = m.vars.at({c->stats_vars[v].op, c->stats_vars[v].order}).adaptive ? 1 : 0;
   for (Device &d : c->devs) {
     HIP_TRY(hipSetDevice(d.hip_id));
     HIP_TRY(cbx::var_tables_upload(d.var_tables, plan.chunks.data(), plan.chunks.size(), plan.bounds.data(),
@@ -470,6 +505,8 @@ static int build_variable_tables(cbx_context *c) {
     if (have_padded)
       HIP_TRY(cbx::var_tables_upload(d.var_tables_padded, padded.chunks.data(), padded.chunks.size(),
                                      padded.bounds.data(), padded_mult.data(), (uint32_t)V + 1));
+    HIP_TRY(cbx::adaptive_tables_upload(d.adaptive_tables, pieces, adaptive.data()));
+    for (int id : d.replicas) HIP_TRY(cbx::adaptive_scratch_alloc(c->replicas[id]->adaptive, d.adaptive_tables));
   }
   c->var_bounds = plan.bounds;
   return CBX_OK;
@@ -715,6 +752,10 @@ static int check_fused_call(cbx_context *c, const char *me, int first, const int
   if (first < 0 || first > c->size) return fail(CBX_ERR_INVALID, "first replica %d out of range", first);
   if (!tasks) return fail(CBX_ERR_INVALID, "%s: null task list (one entry per replica: a task number, or -1)", me);
   if (flags & ~CBX_STEP_DISCARD_TASK_OUTPUTS) return fail(CBX_ERR_INVALID, "%s: unknown flag bits 0x%x", me, flags);
+  if (c->adaptive_on())
+    return fail(CBX_ERR_UNSUPPORTED, "%s: layer-wise adaptive rates are on (cbx_set_adaptive_rate); the adaptive step "
+                "needs its norm pass first and is not fused into a barrier, use cbx_replica_optimise and "
+                "cbx_synchronise", me);
   const int size = c->size;
   for (int id = 0; id < size; ++id) {
     if (tasks[id] < -1) return fail(CBX_ERR_INVALID, "%s: tasks[%d] = %d is neither a task number nor -1", me, id, tasks[id]);
@@ -1454,6 +1495,7 @@ int cbx_add_model(cbx_context *c) {
         HIP_TRY(hipMemcpyAsync(replica_dev(d, *r, kind), replica_dev(d, src, kind), d.stride, hipMemcpyDeviceToDevice,
                                d.stream));
       HIP_TRY(cbx::clip_scratch_alloc(r->clip, c->n));  // a record of its own, all zeros
+      if (d.adaptive_tables.dev) HIP_TRY(cbx::adaptive_scratch_alloc(r->adaptive, d.adaptive_tables));
       HIP_TRY(hipStreamSynchronize(d.stream));
       pthread_mutex_lock(&r->lock);  // :433-435
       c->locked[id] = 1;
@@ -1502,6 +1544,7 @@ int cbx_del_model(cbx_context *c) {
       if (r->client) (void)hipEventDestroy(r->client);
       r->client = nullptr;
       cbx::clip_scratch_free(r->clip);  // every stream has drained above
+      cbx::adaptive_scratch_free(r->adaptive);
       d.replicas.erase(std::remove(d.replicas.begin(), d.replicas.end(), id), d.replicas.end());
     }
     pthread_mutex_unlock(&r->lock);
@@ -1719,13 +1762,39 @@ int cbx_set_gradient_clip(cbx_context *c, float max_norm, int skip_nonfinite) {
   return CBX_OK;
 }
 
+int cbx_set_adaptive_rate(cbx_context *c, float trust, float epsilon, int mode) {
+  TRY(check_ctx(c));
+  if (!(trust >= 0.0f) || std::isinf(trust))
+    return fail(CBX_ERR_INVALID, "cbx_set_adaptive_rate: trust %g is negative, NaN or infinite", (double)trust);
+  if (!(epsilon >= 0.0f) || std::isinf(epsilon))
+    return fail(CBX_ERR_INVALID, "cbx_set_adaptive_rate: epsilon %g is negative, NaN or infinite", (double)epsilon);
+  if (mode != 0 && mode != 1)
+    return fail(CBX_ERR_INVALID, "cbx_set_adaptive_rate: mode %d is neither 0 (LARS) nor 1 (LARC)", mode);
+  c->adaptive_trust = trust;
+  c->adaptive_epsilon = epsilon;
+  c->adaptive_mode = mode;
+  c->adaptive_norm_policy = cbx::adaptive_norm_policy();
+  return CBX_OK;
+}
+
+int cbx_set_adaptive_kernel_policy(cbx_context *c, int policy) {
+  TRY(check_ctx(c));
+  if (policy != 0 && policy != 1) return fail(CBX_ERR_INVALID, "cbx_set_adaptive_kernel_policy: policy must be 0 or 1");
+  c->adaptive_policy = policy;
+  return CBX_OK;
+}
+
 // Float ranges [lo, hi) of a replica's buffers.  nullptr: the whole model
 // with the solver's one rate (sma_optimise_kernel); else each range with the
 // rate of its variables (sma_optimise_variables_kernel), one launch each.
 using VarRanges = std::vector<std::pair<uint32_t, uint32_t>>;
 
 // crossbowKernelOptimiserSMA (sma.cu:3-100) on one replica, whole or ranged.
-static int sma_task_step(cbx_context *c, Replica &r, Device &d, int task, void *stream, const VarRanges *ranges) {
+// `adaptive`: the whole model with layer-wise adaptive rates
+// (adaptive_rate_kernels.hip); `ranges` then only says whether the registered
+// multipliers apply.
+static int sma_task_step(cbx_context *c, Replica &r, Device &d, int task, void *stream, const VarRanges *ranges,
+                         bool adaptive = false) {
   SolverConf &conf = r.conf;
   if (conf.momentum > 0 && conf.momentumMethod == 1)
     return fail(CBX_ERR_UNSUPPORTED, "Nesterov's momentum has been disabled");  // sma.cu:46-48
@@ -1752,6 +1821,29 @@ static int sma_task_step(cbx_context *c, Replica &r, Device &d, int task, void *
   // The replica must not be updated while the last synchronise() still uses
   // it (the reference's forward kernels wait on replica->updated).
   if (st != d.stream && d.step_event) HIP_TRY(hipStreamWaitEvent(st, d.step_event, 0));
+  if (adaptive) {
+    // Both launches of the reduction first, on the same stream: the trust
+    // table is in the replica's scratch when the step reads it.
+    if (!r.adaptive.dev || !d.adaptive_tables.dev || d.adaptive_tables.nvars != d.var_tables.nvars)
+      return fail(CBX_ERR_STATE, "replica %d has no adaptive-rate scratch", r.id);
+    const cbx::AdaptiveParams prm = {c->adaptive_trust, c->adaptive_epsilon, conf.weightDecay, c->adaptive_mode};
+    HIP_TRY(cbx::launch_variable_norms(reinterpret_cast<const float *>(a.w), reinterpret_cast<const float *>(a.g),
+                                       d.adaptive_tables, r.adaptive, prm, c->adaptive_norm_policy, st));
+    cbx::VarOptArgs v;
+    std::memset(&v, 0, sizeof(v));
+    v.w = a.w;
+    v.g = a.g;
+    v.last = a.last;
+    v.s = a.s;
+    v.rate = a.rate;
+    v.momentum = a.momentum;
+    v.wd = a.wd;
+    cfg.policy = c->adaptive_policy;  // cbx_set_adaptive_kernel_policy
+    HIP_TRY(cbx::launch_sma_optimise_adaptive(d.var_tables, v, ranges ? d.var_tables.mult : d.adaptive_tables.ones(),
+                                              r.adaptive.trust(), cfg, st, {}));
+    if (st != d.stream && !c->fault_skip_task_wait) TRY(defer_task_wait(d, st));
+    return CBX_OK;
+  }
   const bool clip = c->clip_on();
   if (clip) {
     // The whole-model reduction first, on the same stream: S, K, the scale
@@ -1796,6 +1888,27 @@ static int replica_optimise_impl(cbx_context *c, int id, int task, void *stream)
                 "cbx_replica_optimise with gradient clipping on: update model %d (%s) steps the base model on the sync "
                 "stream and has no clipped step; clipping covers SMA and SYNCHRONOUSEAMSGD",
                 type, type == CBX_UPDATE_WORKER ? "WORKER" : "DEFAULT");
+  if (c->adaptive_on()) {
+    if (type == CBX_UPDATE_WORKER || type == CBX_UPDATE_DEFAULT)
+      return fail(CBX_ERR_UNSUPPORTED,
+                  "cbx_replica_optimise with layer-wise adaptive rates on: update model %d (%s) steps the base model "
+                  "on the sync stream and has no adaptive step; turn them off (cbx_set_adaptive_rate) for "
+                  "cbx_replica_optimise, they cover SMA and SYNCHRONOUSEAMSGD",
+                  type, type == CBX_UPDATE_WORKER ? "WORKER" : "DEFAULT");
+    if (c->clip_on())
+      return fail(CBX_ERR_UNSUPPORTED,
+                  "cbx_replica_optimise with layer-wise adaptive rates and gradient clipping both on: the two are not "
+                  "composed yet; turn one off (cbx_set_gradient_clip or cbx_set_adaptive_rate)");
+    if (type != CBX_UPDATE_SMA && type != CBX_UPDATE_SYNCHRONOUSEAMSGD)
+      return fail(CBX_ERR_UNSUPPORTED, "update model %d has no optimiser step in this library", type);
+    if (!c->var_refusal.empty())
+      return fail(CBX_ERR_UNSUPPORTED, "cbx_replica_optimise with layer-wise adaptive rates (cbx_set_adaptive_rate): %s",
+                  c->var_refusal.c_str());
+    if (!r.adaptive.dev) return fail(CBX_ERR_STATE, "replica %d has no adaptive-rate scratch", id);
+    const VarRanges whole(1, {0u, (uint32_t)c->n});
+    const bool multipliers = c->variable_rates && c->model.conf.irregular > 0;
+    return sma_task_step(c, r, d, task, stream, multipliers ? &whole : nullptr, true);
+  }
   if (type == CBX_UPDATE_WORKER)
     return ssgd_worker_step(c, r, d, task, stream ? reinterpret_cast<hipStream_t>(stream) : d.stream);
   if (type == CBX_UPDATE_DEFAULT)
@@ -1821,6 +1934,10 @@ static int replica_optimise_variables_impl(cbx_context *c, int id, int task, int
   if (type != CBX_UPDATE_SMA && type != CBX_UPDATE_SYNCHRONOUSEAMSGD)
     return fail(CBX_ERR_UNSUPPORTED, "update model %d has no per-operator optimiser step in this library", type);
   if (op < 0 || op >= c->model.ops) return fail(CBX_ERR_INVALID, "operator %d out of range [0, %d)", op, c->model.ops);
+  if (c->adaptive_on())
+    return fail(CBX_ERR_UNSUPPORTED,
+                "cbx_replica_optimise_variables with layer-wise adaptive rates on (cbx_set_adaptive_rate): the "
+                "per-operator adaptive step is not built; step the whole model with cbx_replica_optimise");
   if (c->clip_on())
     return fail(CBX_ERR_UNSUPPORTED,
                 "cbx_replica_optimise_variables with gradient clipping on: the global norm does not exist until every "
@@ -2261,6 +2378,23 @@ int cbx_replica_clip_stats(cbx_context *c, int id, cbx_clip_stats *out) {
   HIP_TRY(hipSetDevice(d.hip_id));
   HIP_TRY(hipStreamSynchronize(d.stream));
   HIP_TRY(hipMemcpy(out, r.clip.record(), sizeof(*out), hipMemcpyDeviceToHost));
+  return CBX_OK;
+}
+
+int cbx_replica_adaptive_stats(cbx_context *c, int id, cbx_adaptive_stats *out, int count) {
+  TRY(check_replica(c, id, true));
+  if (!out) return fail(CBX_ERR_INVALID, "cbx_replica_adaptive_stats: null result");
+  Replica &r = *c->replicas[id];
+  Device &d = c->devs[r.local];
+  if (!r.adaptive.dev)
+    return fail(CBX_ERR_STATE, "replica %d has no adaptive-rate scratch%s%s", id, c->var_refusal.empty() ? "" : ": ",
+                c->var_refusal.c_str());
+  if (count < 0 || count > (int)r.adaptive.nvars)
+    return fail(CBX_ERR_INVALID, "cbx_replica_adaptive_stats: count %d out of range [0, %u]", count, r.adaptive.nvars);
+  TRY(flush_task_waits(c));
+  HIP_TRY(hipSetDevice(d.hip_id));
+  HIP_TRY(hipStreamSynchronize(d.stream));
+  if (count > 0) HIP_TRY(hipMemcpy(out, r.adaptive.records(), (size_t)count * sizeof(*out), hipMemcpyDeviceToHost));
   return CBX_OK;
 }
 

@@ -37,6 +37,7 @@
 
 #include "../../include/crossbow_sma.h"
 #include "bucket_pipeline.h"
+#include "adaptive_internal.h"
 #include "clip_internal.h"
 #include "sma_internal.h"
 #include "stats_internal.h"
@@ -274,6 +275,8 @@ struct Variable {
   // variable.c: read by the per-variable replica step (cbx_set_variable_learning_rates,
   // cbx_replica_optimise_variables) when conf.irregular > 0, by nothing else
   float lr_multiplier = 1.0f;
+  // cbx_set_model_variable_adaptive_rate: false excludes it from the trust ratio
+  bool adaptive = true;
 };
 
 struct ModelDef {
@@ -312,6 +315,10 @@ struct Replica {
   // of partials on its device, allocated with the replica and freed with it.
   // Per replica, so replicas stepping on different task streams share nothing.
   cbx::ClipScratch clip;
+  // Layer-wise adaptive rates (cbx_set_adaptive_rate): this replica's records,
+  // trust table and slab, allocated with the replica where the model has
+  // variable ranges, and freed with it.
+  cbx::AdaptiveScratch adaptive;
 };
 
 enum TimingEv { EV_START = 0, EV_A, EV_AR, EV_B, EV_H2D0, EV_H2D1, EV_D2H0, EV_D2H1, EV_COUNT };
@@ -401,6 +408,8 @@ struct Device {
   // cbx_step_and_synchronise_variables: the same tables over the padded length,
   // the pad a last pseudo-variable of multiplier 1 (build_padded_optimise_plan)
   cbx::VarTables var_tables_padded;
+  // cbx_set_adaptive_rate: the reduction's piece table and the variables' enable flags
+  cbx::AdaptiveTables adaptive_tables;
   int num_cus = 256;
   // Arena: [base data][base gradient(ctrl+acc)][base diff(ctrl+D)][base last]
   //        then per replica [data][diff][last][gradient].
@@ -530,6 +539,13 @@ struct cbx_context {
   bool clip_skip_nonfinite = false;
   int clip_norm_policy = cbx::kClipNormPolicy;  // the norm pass's loads of g (clip_internal.h)
   bool clip_on() const { return clip_max_norm > 0.0f || clip_skip_nonfinite; }
+  // cbx_set_adaptive_rate: a trust coefficient of zero is off.
+  float adaptive_trust = 0.0f;
+  float adaptive_epsilon = 0.0f;
+  int adaptive_mode = 0;
+  int adaptive_norm_policy = cbx::kAdaptiveNormPolicy;  // the norm pass's loads of w and g (adaptive_internal.h)
+  int adaptive_policy = 1;  // cbx_set_adaptive_kernel_policy: the step's loads and stores, 1 nontemporal as the aux kernels'
+  bool adaptive_on() const { return adaptive_trust > 0.0f; }
   // BN operators whose running statistics travel with the checkpoint
   // (executioncontext.c:2352-2364): op id -> per-local-device buffers.
   struct BnStats {
@@ -889,6 +905,7 @@ inline void close_device(Device &d) {
   cbx::stats_free(d.stats);
   cbx::var_tables_free(d.var_tables);
   cbx::var_tables_free(d.var_tables_padded);
+  cbx::adaptive_tables_free(d.adaptive_tables);
   if (d.host) (void)hipHostFree(d.host);
   if (d.synched) (void)hipEventDestroy(d.synched);
   for (int k = 0; k < EV_COUNT; ++k)

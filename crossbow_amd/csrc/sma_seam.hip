@@ -95,7 +95,12 @@ struct cbx_sma_plan {
     // cbx_sma_plan_optimise_clipped: record and slab per slot, allocated on a
     // slot's first use (clip_mu held).
     cbx::ClipScratch clip[kClipSlots];
+    // cbx_sma_plan_set_adaptive: the reduction's tables and one scratch per slot
+    cbx::AdaptiveTables adaptive_tables;
+    std::vector<cbx::AdaptiveScratch> adaptive;
   };
+  int adaptive_norm_policy = cbx::kAdaptiveNormPolicy;
+  std::vector<long long> var_elements;  // cbx_sma_plan_set_variables: the list itself, for the piece table
   std::mutex clip_mu;
   int clip_norm_policy = cbx::clip_norm_policy();
   std::vector<uint32_t> var_bounds;  // cbx_sma_plan_set_variables: nvars + 1 running offsets (empty: not set)
@@ -315,6 +320,8 @@ int cbx_sma_plan_free(cbx_sma_plan *p) {
     cbx::stats_free(d.stats);
     cbx::var_tables_free(d.var_tables);
     for (cbx::ClipScratch &cs : d.clip) cbx::clip_scratch_free(cs);
+    cbx::adaptive_tables_free(d.adaptive_tables);
+    for (cbx::AdaptiveScratch &as : d.adaptive) cbx::adaptive_scratch_free(as);
     for (hipEvent_t e : d.ev_a) (void)hipEventDestroy(e);
     for (hipEvent_t e : d.ev_r) (void)hipEventDestroy(e);
     if (d.comm_stream) (void)hipStreamDestroy(d.comm_stream);
@@ -1132,8 +1139,144 @@ int cbx_sma_plan_set_variables(cbx_sma_plan *p, const long long *var_elements, c
     HIP_TRY(hipDeviceSynchronize());  // no step in flight still reads the tables being replaced
     HIP_TRY(cbx::var_tables_upload(d.var_tables, plan.chunks.data(), plan.chunks.size(), plan.bounds.data(),
                                    multipliers, (uint32_t)nvars));
+    // the adaptive tables belong to the list that has just been replaced
+    cbx::adaptive_tables_free(d.adaptive_tables);
+    for (cbx::AdaptiveScratch &as : d.adaptive) cbx::adaptive_scratch_free(as);
+    d.adaptive.clear();
   }
   p->var_bounds = plan.bounds;
+  p->var_elements.assign(var_elements, var_elements + nvars);
+  return CBX_OK;
+}
+
+int cbx_sma_plan_set_adaptive(cbx_sma_plan *p, const unsigned char *enable, int slots) {
+  TraceRange trace("cbx_sma_plan_set_adaptive");
+  if (!p) return fail(CBX_ERR_INVALID, "null plan");
+  if (p->var_bounds.empty()) return fail(CBX_ERR_STATE, "cbx_sma_plan_set_adaptive before cbx_sma_plan_set_variables");
+  if (slots < 1 || slots > cbx_sma_plan::kClipSlots)
+    return fail(CBX_ERR_INVALID, "cbx_sma_plan_set_adaptive: %d slots out of range [1, %d]", slots,
+                cbx_sma_plan::kClipSlots);
+  cbx::StatsPlan pieces;
+  if (!cbx::build_stats_plan(p->var_elements.data(), (int)p->var_elements.size(), p->n, &pieces))
+    return fail(CBX_ERR_INVALID, "cbx_sma_plan_set_adaptive: the variables do not sum to the plan's %lld elements",
+                (long long)p->n);
+  p->adaptive_norm_policy = cbx::adaptive_norm_policy();
+  for (auto &d : p->devs) {
+    HIP_TRY(hipSetDevice(d.hip_id));
+    HIP_TRY(hipDeviceSynchronize());  // no step in flight still reads what is being replaced
+    for (cbx::AdaptiveScratch &as : d.adaptive) cbx::adaptive_scratch_free(as);
+    d.adaptive.assign((size_t)slots, cbx::AdaptiveScratch());
+    HIP_TRY(cbx::adaptive_tables_upload(d.adaptive_tables, pieces, enable));
+    for (cbx::AdaptiveScratch &as : d.adaptive) HIP_TRY(cbx::adaptive_scratch_alloc(as, d.adaptive_tables));
+  }
+  return CBX_OK;
+}
+
+namespace {
+
+// The slot's scratch on plan device k, which becomes the current device.
+int adaptive_slot(cbx_sma_plan *p, const char *what, int k, int slot, cbx::AdaptiveScratch **out) {
+  if (!p) return fail(CBX_ERR_INVALID, "null plan");
+  if (k < 0 || k >= (int)p->devs.size()) return fail(CBX_ERR_INVALID, "plan device %d out of range", k);
+  auto &d = p->devs[k];
+  if (!d.adaptive_tables.dev) return fail(CBX_ERR_STATE, "%s before cbx_sma_plan_set_adaptive", what);
+  if (slot < 0 || slot >= (int)d.adaptive.size())
+    return fail(CBX_ERR_INVALID, "%s: slot %d out of range [0, %d)", what, slot, (int)d.adaptive.size());
+  HIP_TRY(hipSetDevice(d.hip_id));
+  *out = &d.adaptive[(size_t)slot];
+  return CBX_OK;
+}
+
+}  // namespace
+
+// Both doors of the adaptive step: `loads` < 0 is the plan's choice for the
+// norm pass; `ev`, when given, are the (start, stop) pairs of the pass, the
+// trust kernel and the step, stamped by the dispatches themselves.
+static int plan_optimise_adaptive(cbx_sma_plan *p, const char *me, int k, int slot, void *stream, float *w, float *g,
+                                  float *last, float *s, float learning_rate, float momentum, float weight_decay,
+                                  float trust, float epsilon, int mode, int loads, const hipEvent_t *ev) {
+  if (!p) return fail(CBX_ERR_INVALID, "null plan");
+  if (!(trust >= 0.0f) || std::isinf(trust))
+    return fail(CBX_ERR_INVALID, "%s: trust %g is negative, NaN or infinite", me, (double)trust);
+  if (!(epsilon >= 0.0f) || std::isinf(epsilon))
+    return fail(CBX_ERR_INVALID, "%s: epsilon %g is negative, NaN or infinite", me, (double)epsilon);
+  if (mode != 0 && mode != 1) return fail(CBX_ERR_INVALID, "%s: mode %d is neither 0 (LARS) nor 1 (LARC)", me, mode);
+  if (!w || !g || !s || (momentum > 0.0f && !last)) return fail(CBX_ERR_INVALID, "%s: missing buffers", me);
+  if (!aligned16(w) || !aligned16(g) || !aligned16(s) || (momentum > 0.0f && !aligned16(last)))
+    return fail(CBX_ERR_INVALID, "%s: buffers must be 16-byte aligned", me);
+  cbx::AdaptiveScratch *as = nullptr;
+  TRY(adaptive_slot(p, me, k, slot, &as));
+  auto &d = p->devs[k];
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  cbx::LaunchConfig cfg = cbx::aux_launch_config();
+  cfg.num_cus = d.num_cus;
+  const cbx::AdaptiveParams prm = {trust, epsilon, weight_decay, mode};
+  const cbx::Timing none;
+  HIP_TRY(cbx::launch_variable_norms(w, g, d.adaptive_tables, *as, prm, loads < 0 ? p->adaptive_norm_policy : loads, st,
+                                     ev ? cbx::Timing{ev[0], ev[1]} : none, ev ? cbx::Timing{ev[2], ev[3]} : none));
+  cbx::VarOptArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.w = reinterpret_cast<cbx::v4f *>(w);
+  a.g = reinterpret_cast<cbx::v4f *>(g);
+  a.last = momentum > 0.0f ? reinterpret_cast<cbx::v4f *>(last) : nullptr;
+  a.s = reinterpret_cast<cbx::v4f *>(s);
+  a.rate = -1.0f * learning_rate;  // sma.cu:43
+  a.momentum = momentum;
+  a.wd = weight_decay;
+  HIP_TRY(cbx::launch_sma_optimise_adaptive(d.var_tables, a, d.var_tables.mult, as->trust(), cfg, st,
+                                            ev ? cbx::Timing{ev[4], ev[5]} : none));
+  return CBX_OK;
+}
+
+int cbx_sma_plan_optimise_adaptive(cbx_sma_plan *p, int k, int slot, void *stream, float *w, float *g, float *last,
+                                   float *s, float learning_rate, float momentum, float weight_decay, float trust,
+                                   float epsilon, int mode) {
+  const char *me = "cbx_sma_plan_optimise_adaptive";
+  TraceRange trace(me);
+  return plan_optimise_adaptive(p, me, k, slot, stream, w, g, last, s, learning_rate, momentum, weight_decay, trust,
+                                epsilon, mode, -1, nullptr);
+}
+
+int cbx_sma_plan_optimise_adaptive_timed(cbx_sma_plan *p, int k, int slot, void *stream, float *w, float *g,
+                                         float *last, float *s, float learning_rate, float momentum,
+                                         float weight_decay, float trust, float epsilon, int mode, int loads,
+                                         float *pass_ms, float *reduce_ms, float *step_ms) {
+  const char *me = "cbx_sma_plan_optimise_adaptive_timed";
+  TraceRange trace(me);
+  if (!p) return fail(CBX_ERR_INVALID, "null plan");
+  if (loads < -1 || loads > 1) return fail(CBX_ERR_INVALID, "%s: loads %d out of range [-1, 1]", me, loads);
+  if (!pass_ms || !reduce_ms || !step_ms) return fail(CBX_ERR_INVALID, "%s: null result", me);
+  if (k < 0 || k >= (int)p->devs.size()) return fail(CBX_ERR_INVALID, "plan device %d out of range", k);
+  HIP_TRY(hipSetDevice(p->devs[k].hip_id));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  auto run = [&]() -> int {
+    for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
+    TRY(plan_optimise_adaptive(p, me, k, slot, stream, w, g, last, s, learning_rate, momentum, weight_decay, trust,
+                               epsilon, mode, loads, ev));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipEventElapsedTime(pass_ms, ev[0], ev[1]));
+    HIP_TRY(hipEventElapsedTime(reduce_ms, ev[2], ev[3]));
+    HIP_TRY(hipEventElapsedTime(step_ms, ev[4], ev[5]));
+    return CBX_OK;
+  };
+  const int rc = run();
+  for (hipEvent_t e : ev)
+    if (e) (void)hipEventDestroy(e);
+  return rc;
+}
+
+int cbx_sma_plan_adaptive_stats(cbx_sma_plan *p, int k, int slot, void *stream, cbx_adaptive_stats *out, int count) {
+  TraceRange trace("cbx_sma_plan_adaptive_stats");
+  if (!out) return fail(CBX_ERR_INVALID, "cbx_sma_plan_adaptive_stats: null result");
+  cbx::AdaptiveScratch *as = nullptr;
+  TRY(adaptive_slot(p, "cbx_sma_plan_adaptive_stats", k, slot, &as));
+  if (count < 0 || count > (int)as->nvars)
+    return fail(CBX_ERR_INVALID, "cbx_sma_plan_adaptive_stats: count %d out of range [0, %u]", count, as->nvars);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (count > 0)
+    HIP_TRY(hipMemcpyAsync(out, as->records(), (size_t)count * sizeof(*out), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   return CBX_OK;
 }
 

@@ -360,6 +360,51 @@ class SmaPlan:
                "cbx_sma_plan_clip_stats")
         return {name: getattr(out, name) for name, _ in out._fields_}
 
+    def set_adaptive(self, enable: Optional[Sequence[bool]] = None, slots: int = 1) -> None:
+        """``cbx_sma_plan_set_adaptive`` (after ``set_variables``): which
+        variables take the trust ratio (None: all) and how many scratch
+        slots the plan keeps.  Blocks."""
+        en = (ctypes.c_ubyte * max(1, len(enable)))(*[1 if e else 0 for e in enable]) if enable is not None else None
+        _raise(self.lib, self.lib.cbx_sma_plan_set_adaptive(self._p, en, slots), "cbx_sma_plan_set_adaptive")
+
+    def optimise_adaptive(self, k: int, slot: int, stream: int, w: int, g: int, last: Optional[int], s: int,
+                          learning_rate: float, momentum: float, weight_decay: float, trust: float,
+                          epsilon: float = 0.0, mode: int = 0) -> None:
+        """``cbx_sma_plan_optimise_adaptive``: one task's optimiser step with
+        layer-wise adaptive rates (LARS; ``mode`` 1: LARC) on plan device
+        ``k``: norm pass, trust kernel and step; asynchronous on ``stream``."""
+        _raise(self.lib, self.lib.cbx_sma_plan_optimise_adaptive(
+            self._p, k, slot, stream or None, w, g, last or None, s, ctypes.c_float(learning_rate),
+            ctypes.c_float(momentum), ctypes.c_float(weight_decay), ctypes.c_float(trust), ctypes.c_float(epsilon),
+            mode), "cbx_sma_plan_optimise_adaptive")
+
+    def optimise_adaptive_timed(self, k: int, slot: int, stream: int, w: int, g: int, last: Optional[int], s: int,
+                                learning_rate: float, momentum: float, weight_decay: float, trust: float,
+                                epsilon: float = 0.0, mode: int = 0, loads: int = -1):
+        """``cbx_sma_plan_optimise_adaptive_timed``: ``optimise_adaptive``,
+        blocking; returns (pass ms, trust-kernel ms, step ms) from the three
+        dispatches' own timestamps.  ``loads``: 0 plain, 1 nontemporal loads
+        in the pass, -1 the library's choice."""
+        ms = [ctypes.c_float(-1) for _ in range(3)]
+        _raise(self.lib, self.lib.cbx_sma_plan_optimise_adaptive_timed(
+            self._p, k, slot, stream or None, w, g, last or None, s, ctypes.c_float(learning_rate),
+            ctypes.c_float(momentum), ctypes.c_float(weight_decay), ctypes.c_float(trust), ctypes.c_float(epsilon),
+            mode, loads, *[ctypes.byref(m) for m in ms]), "cbx_sma_plan_optimise_adaptive_timed")
+        return tuple(m.value for m in ms)
+
+    def adaptive_stats(self, k: int, slot: int, stream: int, count: int):
+        """``cbx_sma_plan_adaptive_stats``: the slot's first ``count`` records
+        (blocks on ``stream``), a structured array with the fields of
+        ``cbx_adaptive_stats``."""
+        import numpy as np
+        at = self.lib.cbx_sma_plan_adaptive_stats.argtypes[4]
+        out = np.zeros(max(1, count), dtype=[("w_sq", "<f8"), ("g_sq", "<f8"), ("nonfinite", "<u8"), ("trust", "<f4"),
+                                             ("flags", "<u4")])
+        _raise(self.lib, self.lib.cbx_sma_plan_adaptive_stats(self._p, k, slot, stream or None,
+                                                              ctypes.cast(out.ctypes.data, at), count),
+               "cbx_sma_plan_adaptive_stats")
+        return out[:count]
+
     def set_buckets(self, buckets: int) -> None:
         """G > 1: buckets of the all-reduce pipeline (0 = default 8, 1 = in order)."""
         _raise(self.lib, self.lib.cbx_sma_plan_set_buckets(self._p, buckets), "cbx_sma_plan_set_buckets")

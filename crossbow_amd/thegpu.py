@@ -138,6 +138,32 @@ class TheGPU:
         check(self._L.cbx_replica_clip_stats(self._ctx, id, ctypes.byref(out)))
         return {name: getattr(out, name) for name, _ in out._fields_}
 
+    def set_adaptive_rate(self, trust: float, epsilon: float = 0.0, mode: int = 0) -> int:
+        """``cbx_set_adaptive_rate``: ``replica_optimise`` scales every
+        variable's rate by ``trust`` x |w_v| / (|g_v| + weight decay x |w_v| +
+        ``epsilon``), taken on the device (LARS; ``mode`` 1, LARC, caps the
+        ratio at 1).  ``trust`` 0: off."""
+        return check(self._L.cbx_set_adaptive_rate(self._ctx, ctypes.c_float(trust), ctypes.c_float(epsilon), mode))
+
+    def set_adaptive_kernel_policy(self, policy: int) -> int:
+        """``cbx_set_adaptive_kernel_policy``: 0 plain, 1 nontemporal loads and
+        stores in the adaptive step kernel."""
+        return check(self._L.cbx_set_adaptive_kernel_policy(self._ctx, policy))
+
+    def set_model_variable_adaptive_rate(self, id: int, order: int, enable: bool) -> int:
+        """``cbx_set_model_variable_adaptive_rate``: ``enable`` False keeps
+        variable (id, order) out of the scaling (biases, batch-norm scales)."""
+        return check(self._L.cbx_set_model_variable_adaptive_rate(self._ctx, id, order, int(enable)))
+
+    def replica_adaptive_stats(self, id: int, count: int) -> np.ndarray:
+        """``cbx_replica_adaptive_stats`` (blocking): the records of the
+        replica's first ``count`` variables, a structured array with the
+        fields of ``cbx_adaptive_stats``."""
+        out = np.zeros(max(1, count), dtype=_lib.ADAPTIVE_STATS_FIELDS)
+        check(self._L.cbx_replica_adaptive_stats(self._ctx, id,
+                                                 ctypes.cast(out.ctypes.data, ctypes.POINTER(_lib.AdaptiveStats)), count))
+        return out[:count]
+
     # ---- solver (SolverConf.GPURegister, SolverConf.java:355-409) ----------
     def setLearningRateDecayPolicyFixed(self, rate: float) -> int:
         return check(self._L.cbx_set_learning_rate_decay_policy_fixed(self._ctx, rate))

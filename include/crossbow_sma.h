@@ -850,6 +850,84 @@ typedef struct cbx_clip_stats {
  * record back.  All zeros before the replica's first step with the feature
  * on.                                                                       */
 int cbx_replica_clip_stats (cbx_context *ctx, int id, cbx_clip_stats *out);
+
+/* ---- layer-wise adaptive rates (LARS, LARC) ----------------------------- */
+/* An extension: the reference has one rate per model and a fixed multiplier
+ * per variable, nothing that follows the norms.  Opt-in, off by default; off,
+ * every call launches exactly what it launches without it.  On, every
+ * cbx_replica_optimise under SMA (7) or SYNCHRONOUSEAMSGD (3) first reduces
+ * the replica's weights and gradient per variable on the device, on the
+ * caller's stream, with no host round trip
+ * (crossbow_amd/csrc/adaptive_rate_kernels.hip), and steps variable v with
+ * its rate scaled by the trust ratio eta * |w_v| / (|g_v| + beta * |w_v| + eps).
+ * Per call, with eta = trust, eps = epsilon, beta the stepping replica's
+ * weight decay, and w, g, last the replica's buffers as the backward pass
+ * left them, over exactly the model's n floats (a buffer's pad is never read
+ * by the reduction), for every variable v of the registered list:
+ *   1. W_v = sum of (double)w_i * (double)w_i and G_v = sum of
+ *      (double)g_i * (double)g_i over the floats of v that are finite in that
+ *      buffer, accumulated in fp64 from the first add in an order that is a
+ *      fixed function of the variable list alone (never of the CU count,
+ *      cbx_set_aux_kernel_config or the stream); K_v = the count of
+ *      non-finite floats of v in w plus those in g.
+ *   2. nw = sqrt (W_v); ng = sqrt (G_v);
+ *      den = (ng + (double)beta * nw) + (double)eps;
+ *      t_v = (float)(((double)eta * nw) / den), in fp64 with IEEE sqrt and
+ *      divide, rounded to float once.  Mode 1 (LARC): t_v = min (t_v, 1.0f).
+ *      t_v = 1.0f for an excluded variable, for a degenerate one (W_v == 0,
+ *      G_v == 0 or K_v > 0; a non-finite value then propagates exactly as in
+ *      the plain step) and for a variable without floats.
+ *   3. The per-variable step of cbx_set_variable_learning_rates with
+ *      r_v = (rate * m_v) * t_v, two fp32 multiplies in that order, rate = -lr,
+ *      m_v the registered multiplier where cbx_set_variable_learning_rates is
+ *      on and conf.irregular > 0, else 1.  Everything else is unchanged; s, w,
+ *      g and last are written exactly where that step writes them.  The norms
+ *      are taken on the raw g, before weight decay.
+ *   4. The replica's record of every variable on the device is updated.
+ * The host side of the step (learning-rate query, _copy, the Nesterov and
+ * missing-`last` refusals, the wait for the last barrier, the deferred
+ * sync-stream wait) happens exactly as in the plain step.  The step's block
+ * and unroll are cbx_set_aux_kernel_config's, its load/store policy
+ * cbx_set_adaptive_kernel_policy's.  The path moves 36 n bytes (8 n for the pass, 28 n
+ * for the step with momentum) against the per-variable step's 28 n.
+ * trust == 0: off.  A negative, NaN or infinite trust or epsilon, or a mode
+ * other than 0 / 1, is CBX_ERR_INVALID.  May be called before or after
+ * cbx_set_model_manager.  While the feature is on, CBX_ERR_UNSUPPORTED, each
+ * before anything is changed: cbx_replica_optimise under WORKER and DEFAULT;
+ * cbx_replica_optimise with gradient clipping also on (turn one of them off);
+ * cbx_replica_optimise_variables (step the whole model with
+ * cbx_replica_optimise); every cbx_step_and_synchronise* call (use
+ * cbx_replica_optimise and cbx_synchronise); and a model without variable
+ * ranges (cbx_set_variable_learning_rates).  With several devices per context
+ * every local device carries its own tables and every replica its own
+ * scratch; that path has not run on several devices.                        */
+int cbx_set_adaptive_rate (cbx_context *ctx, float trust, float epsilon, int mode);
+/* Loads and stores of the adaptive step kernel: 0 plain, 1 nontemporal (the
+ * default, as the other per-task kernels run).  cbx_set_aux_kernel_config
+ * carries no policy, and the fused SMA kernel's switch (cbx_set_kernel_config)
+ * does not reach this kernel.  Anything else is CBX_ERR_INVALID.            */
+int cbx_set_adaptive_kernel_policy (cbx_context *ctx, int policy);
+/* enable == 0 excludes variable (id, order) from the scaling (t_v = 1): the
+ * usual treatment of biases and batch-norm scales.  The default is 1.  After
+ * cbx_set_model_manager it blocks: every device is drained, then its table is
+ * updated, as for cbx_set_model_variable_learning_rate_multiplier.          */
+int cbx_set_model_variable_adaptive_rate (cbx_context *ctx, int id, int order, int enable);
+#define CBX_ADAPTIVE_APPLIED    1u  /* cbx_adaptive_stats.flags: t_v is rule 2's ratio    */
+#define CBX_ADAPTIVE_EXCLUDED   2u  /* the variable is excluded                            */
+#define CBX_ADAPTIVE_DEGENERATE 4u  /* W_v == 0, G_v == 0 or K_v > 0                       */
+#define CBX_ADAPTIVE_CAPPED     8u  /* mode 1 took the ratio down to 1                     */
+typedef struct cbx_adaptive_stats {
+  double w_sq;                      /* W_v of the last adaptive step                 */
+  double g_sq;                      /* G_v                                           */
+  unsigned long long nonfinite;     /* K_v                                           */
+  float  trust;                     /* t_v as the step read it                       */
+  unsigned int flags;               /* CBX_ADAPTIVE_*; 0 for a variable without floats */
+} cbx_adaptive_stats;               /* 32 bytes, no implicit padding                 */
+/* Blocking: drains as cbx_replica_clip_stats does, then copies the first
+ * `count` variables' records of replica `id` back, in offset order
+ * (cbx_model_variable_info).  All zeros before the replica's first adaptive
+ * step.  count outside [0, variables] is CBX_ERR_INVALID.                   */
+int cbx_replica_adaptive_stats (cbx_context *ctx, int id, cbx_adaptive_stats *out, int count);
 /* Entries in local device `local`'s table of deferred task-stream waits
  * (see cbx_replica_optimise; at most 64). */
 int cbx_task_wait_count (cbx_context *ctx, int local);
@@ -1434,6 +1512,37 @@ int cbx_sma_plan_clip_stats (cbx_sma_plan *plan, int k, int slot, void *stream, 
  * timestamps.                                                              */
 int cbx_sma_plan_gradient_norm (cbx_sma_plan *plan, int k, int slot, void *stream, const float *g, float max_norm,
                                 int skip_nonfinite, int loads, float *pass_ms, float *reduce_ms);
+/* The step with layer-wise adaptive rates (cbx_set_adaptive_rate: the same
+ * semantics, kernels and bits on the same data and variable list), over
+ * caller-owned, unpadded, 16-byte-aligned buffers of the plan's `elements`
+ * floats on plan device k, asynchronously on `stream`: pass, trust kernel and
+ * step.  Nothing past float elements - 1 is read or written.
+ * cbx_sma_plan_set_adaptive comes after cbx_sma_plan_set_variables (whose
+ * multipliers the step applies; calling that again drops the adaptive tables):
+ * enable[0..nvars) excludes the variables whose byte is 0 (NULL: none), and
+ * `slots` in [1, 64] is the number of plan-owned scratch slots (records, trust
+ * table and slab), so that many replicas can be in flight; steps that share a
+ * slot are ordered by the caller.  It blocks (every plan device is drained).
+ * trust, epsilon and mode as in cbx_set_adaptive_rate, except that trust == 0
+ * is not "off" here but a step whose ratios are 0; the argument checks are those of
+ * cbx_sma_plan_optimise_clipped.  cbx_sma_plan_adaptive_stats blocks on
+ * `stream`, then copies the slot's first `count` records back: all zeros
+ * before the slot's first step.                                            */
+int cbx_sma_plan_set_adaptive (cbx_sma_plan *plan, const unsigned char *enable, int slots);
+int cbx_sma_plan_optimise_adaptive (cbx_sma_plan *plan, int k, int slot, void *stream, float *w, float *g,
+                                    float *last, float *s, float learning_rate, float momentum, float weight_decay,
+                                    float trust, float epsilon, int mode);
+int cbx_sma_plan_adaptive_stats (cbx_sma_plan *plan, int k, int slot, void *stream, cbx_adaptive_stats *out,
+                                 int count);
+/* cbx_sma_plan_optimise_adaptive for a measurement: the same three launches
+ * and the same bits, blocking on `stream`, with the device milliseconds of
+ * the pass, the trust kernel and the step from the dispatches' own
+ * timestamps.  loads: 0 plain, 1 nontemporal loads of w and g in the pass,
+ * -1 the library's choice.                                                  */
+int cbx_sma_plan_optimise_adaptive_timed (cbx_sma_plan *plan, int k, int slot, void *stream, float *w, float *g,
+                                          float *last, float *s, float learning_rate, float momentum,
+                                          float weight_decay, float trust, float epsilon, int mode, int loads,
+                                          float *pass_ms, float *reduce_ms, float *step_ms);
 /* The same seam for update model WORKER (synchronous SGD):
  * crossbowSynchronisationSynchronousSGD (synch/synchronoussgd.c:13-106) ->
  * cbx_ssgd_plan_step, over acc[k] = baseModels[k]->gradient->dev (the
