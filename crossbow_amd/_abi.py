@@ -128,6 +128,7 @@ SIGNATURES = {
     "cbx_step_and_synchronise_variables": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
     "cbx_step_and_synchronise_clipped": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
     "cbx_step_and_synchronise_clipped_variables": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
+    "cbx_step_and_synchronise_adaptive": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
     "cbx_step_and_synchronise_elastic": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
     "cbx_step_and_synchronise_elastic_clipped_variables": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
     "cbx_step_and_synchronise_ssgd": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
@@ -225,6 +226,8 @@ SIGNATURES = {
     "cbx_sma_plan_step_and_optimise_clipped_variables": (_I, [_P, _PP, _PP, _PP, _I, _IP, _PP, _PP, _PP, _PP, _IP,
                                                               _IP, _IP, _FP, _IP, _F, _I, _F, _F, _F, _F, _I,
                                                               _c.c_uint]),
+    "cbx_sma_plan_step_and_optimise_adaptive": (_I, [_P, _PP, _PP, _PP, _I, _IP, _PP, _PP, _PP, _PP, _IP, _IP, _IP,
+                                                     _FP, _IP, _F, _F, _I, _F, _F, _F, _F, _I, _c.c_uint]),
     "cbx_sma_plan_buffer_stats": (_I, [_P, _I, _P, _P, _PP, _I, _LLP, _I, _BS, _BS, _BS, _BS]),
     "cbx_sma_optimise_buffers": (_I, [_P, _P, _P, _P, _P, _c.c_longlong, _F, _F, _F]),
     "cbx_sma_plan_set_variables": (_I, [_P, _LLP, _FP, _I]),

@@ -506,6 +506,7 @@ static int build_variable_tables(cbx_context *c) {
       HIP_TRY(cbx::var_tables_upload(d.var_tables_padded, padded.chunks.data(), padded.chunks.size(),
                                      padded.bounds.data(), padded_mult.data(), (uint32_t)V + 1));
     HIP_TRY(cbx::adaptive_tables_upload(d.adaptive_tables, pieces, adaptive.data()));
+    HIP_TRY(cbx::rate_matrix_alloc(d.rate_matrix, d.adaptive_tables));
     for (int id : d.replicas) HIP_TRY(cbx::adaptive_scratch_alloc(c->replicas[id]->adaptive, d.adaptive_tables));
   }
   c->var_bounds = plan.bounds;
@@ -741,21 +742,27 @@ int cbx_synchronise_staged(cbx_context *c, int first, int clock, int autotune, i
 // on and a stepping replica it runs the norm passes as the clipped call places
 // them and the kernel that is both (task_barrier_clipped_variables_kernels.hip);
 // with one of them off, or nobody stepping, it launches what the call for the
-// other one launches.  Everything else is one code path.
-enum FusedMode { FusedPlain, FusedVariables, FusedClipped, FusedClippedVariables };
+// other one launches.  FusedAdaptive: cbx_step_and_synchronise_adaptive, the one
+// call that passes with layer-wise adaptive rates on: behind the callers'
+// deferred waits it puts every stepping replica's norms in two batched launches
+// on the sync stream and then the kernel that takes its rates from the rate
+// matrix (task_barrier_adaptive_kernels.hip); with the rates off, or nobody
+// stepping, it launches what the plain or the per-variable call launches.
+// Everything else is one code path.
+enum FusedMode { FusedPlain, FusedVariables, FusedClipped, FusedClippedVariables, FusedAdaptive };
 
 // What every fused call checks first, of its arguments and of the devices: the
 // same refusals in the same order for the SMA calls and the elastic one (`me`).
 static int check_fused_call(cbx_context *c, const char *me, int first, const int *tasks, unsigned flags,
-                            const char *instead = nullptr) {
+                            const char *instead = nullptr, bool adaptive_ok = false) {
   TRY(check_manager_q(c));
   if (first < 0 || first > c->size) return fail(CBX_ERR_INVALID, "first replica %d out of range", first);
   if (!tasks) return fail(CBX_ERR_INVALID, "%s: null task list (one entry per replica: a task number, or -1)", me);
   if (flags & ~CBX_STEP_DISCARD_TASK_OUTPUTS) return fail(CBX_ERR_INVALID, "%s: unknown flag bits 0x%x", me, flags);
-  if (c->adaptive_on())
+  if (c->adaptive_on() && !adaptive_ok)
     return fail(CBX_ERR_UNSUPPORTED, "%s: layer-wise adaptive rates are on (cbx_set_adaptive_rate); the adaptive step "
-                "needs its norm pass first and is not fused into a barrier, use cbx_replica_optimise and "
-                "cbx_synchronise", me);
+                "needs its norm pass first and is fused into the one-GPU SMA barrier only, use "
+                "cbx_step_and_synchronise_adaptive, or cbx_replica_optimise and cbx_synchronise", me);
   const int size = c->size;
   for (int id = 0; id < size; ++id) {
     if (tasks[id] < -1) return fail(CBX_ERR_INVALID, "%s: tasks[%d] = %d is neither a task number nor -1", me, id, tasks[id]);
@@ -894,21 +901,34 @@ static int defer_caller_waits(cbx_context *c, Device &d, const std::vector<hipSt
 
 static int step_and_synchronise(cbx_context *c, int first, int clock, int autotune, const int *tasks,
                                 void *const *streams, unsigned flags, FusedMode mode) {
-  const bool variables = mode == FusedVariables || mode == FusedClippedVariables;
+  const bool variables = mode == FusedVariables || mode == FusedClippedVariables || mode == FusedAdaptive;
   const bool clips = mode == FusedClipped || mode == FusedClippedVariables;
-  const char *me = mode == FusedClippedVariables ? "cbx_step_and_synchronise_clipped_variables"
-                   : mode == FusedClipped        ? "cbx_step_and_synchronise_clipped"
-                   : variables                   ? "cbx_step_and_synchronise_variables"
-                                                 : "cbx_step_and_synchronise";
+  const char *me = mode == FusedAdaptive           ? "cbx_step_and_synchronise_adaptive"
+                   : mode == FusedClippedVariables ? "cbx_step_and_synchronise_clipped_variables"
+                   : mode == FusedClipped          ? "cbx_step_and_synchronise_clipped"
+                   : variables                     ? "cbx_step_and_synchronise_variables"
+                                                   : "cbx_step_and_synchronise";
   TraceRange trace(me);
-  TRY(check_fused_call(c, me, first, tasks, flags));
+  TRY(check_fused_call(c, me, first, tasks, flags, nullptr, mode == FusedAdaptive));
   const int type = c->model.type;
+  const bool adaptive = c->adaptive_on();  // only FusedAdaptive comes this far with them on
   if (type == CBX_UPDATE_SYNCHRONOUSEAMSGD && c->elastic_average)
-    return fail(CBX_ERR_UNSUPPORTED, "%s: elastic averaging is on (cbx_set_elastic_average); only the SMA barrier is fused", me);
+    return fail(CBX_ERR_UNSUPPORTED, "%s: elastic averaging is on (cbx_set_elastic_average); only the SMA barrier is "
+                "fused%s", me, adaptive ? ", use cbx_replica_optimise and cbx_synchronise" : "");
   if (type != CBX_UPDATE_SMA && type != CBX_UPDATE_SYNCHRONOUSEAMSGD)
-    return fail(CBX_ERR_UNSUPPORTED, "%s: update model %d; only SMA (7) and SYNCHRONOUSEAMSGD (3) are fused", me, type);
+    return fail(CBX_ERR_UNSUPPORTED, "%s: update model %d; only SMA (7) and SYNCHRONOUSEAMSGD (3) are fused%s", me, type,
+                adaptive ? ", and only they have an adaptive step: turn the rates off (cbx_set_adaptive_rate)" : "");
   const bool clip = c->clip_on();
   const bool per_variable = c->variable_rates && c->model.conf.irregular > 0;
+  if (adaptive && clip)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: layer-wise adaptive rates and gradient clipping are both on: the two are not "
+                "composed yet; turn one off (cbx_set_gradient_clip or cbx_set_adaptive_rate)", me);
+  if (adaptive && !c->var_refusal.empty())
+    return fail(CBX_ERR_UNSUPPORTED, "%s with layer-wise adaptive rates (cbx_set_adaptive_rate): %s; turn them off for "
+                "cbx_step_and_synchronise", me, c->var_refusal.c_str());
+  if (adaptive && !c->devs[0].var_tables_padded.chunks)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: the padded model is too large for the chunk table; use cbx_replica_optimise "
+                "and cbx_synchronise", me);
   if (clip && !clips)
     return fail(CBX_ERR_UNSUPPORTED, "%s: gradient clipping is on; the clipped step needs its norm pass first, use %s, "
                 "or cbx_replica_optimise and cbx_synchronise", me,
@@ -924,12 +944,21 @@ static int step_and_synchronise(cbx_context *c, int first, int clock, int autotu
     return fail(CBX_ERR_UNSUPPORTED, "%s: the padded model is too large for the chunk table", me);
   const SolverConf *ref = nullptr;  // the first stepping replica's configuration (null: nobody steps)
   TRY(check_stepping_replicas(c, me, first, tasks, clip, &ref));
+  const bool adaptive_steps = adaptive && ref != nullptr;  // nobody steps: the plain barrier, no norm launch
+  if (adaptive_steps) {
+    for (int id : d.replicas)
+      if (id >= first && c->locked[id] && tasks[id] >= 0 && !c->replicas[id]->adaptive.dev)
+        return fail(CBX_ERR_STATE, "replica %d has no adaptive-rate scratch", id);
+    if (!d.adaptive_tables.dev || !d.rate_matrix.dev || d.adaptive_tables.nvars != d.var_tables.nvars)
+      return fail(CBX_ERR_STATE, "%s: device %d has no adaptive-rate tables", me, d.g);
+  }
 
   std::vector<float> lr((size_t)c->size, 0.0f);
   TRY(query_rates(c, tasks, lr));  // a `_copy` raised here is honoured by this same call's Phase D
 
   FusedSteps f;
   cbx::TaskBarrierArgs &a = f.a;
+  cbx::ReplicaSteps rs;  // the stepping replicas of an adaptive call, id order
   int k = 0, copies = 0;
   for (int id : d.replicas) {  // increasing id order, sma.c:69
     if (id < first || !c->locked[id]) continue;
@@ -937,6 +966,14 @@ static int step_and_synchronise(cbx_context *c, int first, int clock, int autotu
     a.w[k] = reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_DATA));
     a.s[k] = reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_DIFF));
     if (tasks[id] >= 0) f.step(d, r, k, lr[(size_t)id], streams ? streams[id] : nullptr, clip);
+    if (tasks[id] >= 0 && adaptive_steps) {
+      const int j = rs.count++;
+      rs.w[j] = reinterpret_cast<const float *>(a.w[k]);
+      rs.g[j] = reinterpret_cast<const float *>(a.g[k]);
+      rs.scratch[j] = &r.adaptive;
+      rs.rate[j] = a.rate[k];
+      rs.col[j] = k;
+    }
     if (r.conf.copy) copies++;  // sma.c:113-120, after the queries
     ++k;
   }
@@ -957,14 +994,28 @@ static int step_and_synchronise(cbx_context *c, int first, int clock, int autotu
   // A wait for a caller's stream now sits between the previous step and this
   // launch: its start is a marker of its own, not that step's stop
   // (step_start_event), as after cbx_replica_optimise on a task stream.
-  if (!f.callers.empty()) c->foreign_ops.fetch_add(1, std::memory_order_relaxed);
+  // and so do the two norm launches of an adaptive call
+  if (!f.callers.empty() || adaptive_steps) c->foreign_ops.fetch_add(1, std::memory_order_relaxed);
 
   cbx::LaunchConfig cfg = c->task_barrier_cfg;
   cfg.num_cus = d.num_cus;
   const bool keep = (flags & CBX_STEP_DISCARD_TASK_OUTPUTS) == 0;
+  if (adaptive_steps) {
+    // Every stepping replica's norms in one batched pass and one trust launch,
+    // on the sync stream behind the waits: every gradient is there, and in
+    // order on this stream the launches are behind the previous barrier's use
+    // of every record, trust table and matrix column by construction.  The pad
+    // of the buffers is the matrix's last row (ratio and multiplier 1).
+    const cbx::AdaptiveParams prm = {c->adaptive_trust, c->adaptive_epsilon, ref->weightDecay, c->adaptive_mode};
+    HIP_TRY(cbx::launch_replica_norms(rs, d.adaptive_tables, per_variable ? d.var_tables.mult : d.adaptive_tables.ones(),
+                                      prm, d.rate_matrix, d.var_tables_padded.nvars, c->adaptive_norm_policy, d.stream));
+  }
   const cbx::Timing tm = {step_start_event(c, d, 0), step_stop_event(c, d, EV_A)};
-  HIP_TRY(cbx::pick_task_barrier_launch(a, per_variable ? &d.var_tables_padded : nullptr,
-                                        f.norms.empty() ? nullptr : &f.records, keep, cfg, d.stream, tm));
+  if (adaptive_steps)
+    HIP_TRY(cbx::launch_task_barrier_adaptive(a, d.var_tables_padded, d.rate_matrix, keep, cfg, d.stream, tm));
+  else
+    HIP_TRY(cbx::pick_task_barrier_launch(a, per_variable ? &d.var_tables_padded : nullptr,
+                                          f.norms.empty() ? nullptr : &f.records, keep, cfg, d.stream, tm));
   close_fused_step(c, d);
   TRY(finish_sma_step(c, first));
   return finish_barrier(c, clock, autotune);
@@ -988,6 +1039,11 @@ int cbx_step_and_synchronise_clipped(cbx_context *c, int first, int clock, int a
 int cbx_step_and_synchronise_clipped_variables(cbx_context *c, int first, int clock, int autotune, const int *tasks,
                                                void *const *streams, unsigned flags) {
   return step_and_synchronise(c, first, clock, autotune, tasks, streams, flags, FusedClippedVariables);
+}
+
+int cbx_step_and_synchronise_adaptive(cbx_context *c, int first, int clock, int autotune, const int *tasks,
+                                      void *const *streams, unsigned flags) {
+  return step_and_synchronise(c, first, clock, autotune, tasks, streams, flags, FusedAdaptive);
 }
 
 // The pending task steps of the locked replicas and the one-GPU

@@ -38,6 +38,7 @@
 #include "../../include/crossbow_sma.h"
 #include "bucket_pipeline.h"
 #include "adaptive_internal.h"
+#include "adaptive_steps_internal.h"
 #include "clip_internal.h"
 #include "sma_internal.h"
 #include "stats_internal.h"
@@ -410,6 +411,8 @@ struct Device {
   cbx::VarTables var_tables_padded;
   // cbx_set_adaptive_rate: the reduction's piece table and the variables' enable flags
   cbx::AdaptiveTables adaptive_tables;
+  // cbx_step_and_synchronise_adaptive: the finished rates of one call, nvars + 1 rows
+  cbx::RateMatrix rate_matrix;
   int num_cus = 256;
   // Arena: [base data][base gradient(ctrl+acc)][base diff(ctrl+D)][base last]
   //        then per replica [data][diff][last][gradient].
@@ -906,6 +909,7 @@ inline void close_device(Device &d) {
   cbx::var_tables_free(d.var_tables);
   cbx::var_tables_free(d.var_tables_padded);
   cbx::adaptive_tables_free(d.adaptive_tables);
+  cbx::rate_matrix_free(d.rate_matrix);
   if (d.host) (void)hipHostFree(d.host);
   if (d.synched) (void)hipEventDestroy(d.synched);
   for (int k = 0; k < EV_COUNT; ++k)

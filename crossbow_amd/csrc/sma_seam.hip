@@ -98,6 +98,7 @@ struct cbx_sma_plan {
     // cbx_sma_plan_set_adaptive: the reduction's tables and one scratch per slot
     cbx::AdaptiveTables adaptive_tables;
     std::vector<cbx::AdaptiveScratch> adaptive;
+    cbx::RateMatrix rate_matrix;  // cbx_sma_plan_step_and_optimise_adaptive: the finished rates of one call
   };
   int adaptive_norm_policy = cbx::kAdaptiveNormPolicy;
   std::vector<long long> var_elements;  // cbx_sma_plan_set_variables: the list itself, for the piece table
@@ -321,6 +322,7 @@ int cbx_sma_plan_free(cbx_sma_plan *p) {
     cbx::var_tables_free(d.var_tables);
     for (cbx::ClipScratch &cs : d.clip) cbx::clip_scratch_free(cs);
     cbx::adaptive_tables_free(d.adaptive_tables);
+    cbx::rate_matrix_free(d.rate_matrix);
     for (cbx::AdaptiveScratch &as : d.adaptive) cbx::adaptive_scratch_free(as);
     for (hipEvent_t e : d.ev_a) (void)hipEventDestroy(e);
     for (hipEvent_t e : d.ev_r) (void)hipEventDestroy(e);
@@ -511,14 +513,21 @@ int cbx_sma_plan_step(cbx_sma_plan *p, void *const *streams, float *const *z, fl
 // SeamClippedVariables: cbx_sma_plan_step_and_optimise_clipped_variables, both:
 // the norm passes, then the kernel that clips and reads the plan's variable
 // table (task_barrier_clipped_variables_kernels.hip); when nobody steps, the
+// per-variable launch.  SeamAdaptive: cbx_sma_plan_step_and_optimise_adaptive,
+// the stepping replicas' norms over their slots' scratch in two batched
+// launches on streams[0], then the kernel that takes its rates from the plan's
+// rate matrix (task_barrier_adaptive_kernels.hip); when nobody steps, the
 // per-variable launch.
 namespace {
 int clip_slot(cbx_sma_plan *p, const char *what, int k, int slot, cbx::ClipScratch **out);
-enum SeamMode { SeamPlain, SeamVariables, SeamClipped, SeamClippedVariables };
+enum SeamMode { SeamPlain, SeamVariables, SeamClipped, SeamClippedVariables, SeamAdaptive };
 struct SeamClip {
-  const int *slot = nullptr;
+  const int *slot = nullptr;  // the clipped calls' slots, or the adaptive call's
   float max_norm = 0.0f;
   int skip_nonfinite = 0;
+  // SeamAdaptive: trust, epsilon and the mode of cbx_sma_plan_optimise_adaptive
+  float trust = 0.0f, epsilon = 0.0f;
+  int mode = 0;
 };
 }  // namespace
 
@@ -560,15 +569,27 @@ static int plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *
                                   const int *step, const float *learning_rate, float alpha, float momentum,
                                   float replica_momentum, float weight_decay, int first, unsigned flags,
                                   SeamMode mode, const SeamClip &clip = SeamClip()) {
-  const bool variables = mode == SeamVariables || mode == SeamClippedVariables;
+  const bool adaptive = mode == SeamAdaptive;
+  const bool variables = mode == SeamVariables || mode == SeamClippedVariables || adaptive;
   const bool clipped = mode == SeamClipped || mode == SeamClippedVariables;
-  const char *me = mode == SeamClippedVariables ? "cbx_sma_plan_step_and_optimise_clipped_variables"
-                   : clipped                    ? "cbx_sma_plan_step_and_optimise_clipped"
-                   : variables                  ? "cbx_sma_plan_step_and_optimise_variables"
-                                                : "cbx_sma_plan_step_and_optimise";
+  const char *me = adaptive                       ? "cbx_sma_plan_step_and_optimise_adaptive"
+                   : mode == SeamClippedVariables ? "cbx_sma_plan_step_and_optimise_clipped_variables"
+                   : clipped                      ? "cbx_sma_plan_step_and_optimise_clipped"
+                   : variables                    ? "cbx_sma_plan_step_and_optimise_variables"
+                                                  : "cbx_sma_plan_step_and_optimise";
   TraceRange trace(me);
   if (!p) return fail(CBX_ERR_INVALID, "null plan");
   if (variables && p->var_bounds.empty()) return fail(CBX_ERR_STATE, "%s before cbx_sma_plan_set_variables", me);
+  if (adaptive) {
+    if (p->devs.empty() || !p->devs[0].adaptive_tables.dev || !p->devs[0].rate_matrix.dev)
+      return fail(CBX_ERR_STATE, "%s before cbx_sma_plan_set_adaptive", me);
+    if (!(clip.trust >= 0.0f) || std::isinf(clip.trust))
+      return fail(CBX_ERR_INVALID, "%s: trust %g is negative, NaN or infinite", me, (double)clip.trust);
+    if (!(clip.epsilon >= 0.0f) || std::isinf(clip.epsilon))
+      return fail(CBX_ERR_INVALID, "%s: epsilon %g is negative, NaN or infinite", me, (double)clip.epsilon);
+    if (clip.mode != 0 && clip.mode != 1)
+      return fail(CBX_ERR_INVALID, "%s: mode %d is neither 0 (LARS) nor 1 (LARC)", me, clip.mode);
+  }
   if (clipped && (!(clip.max_norm >= 0.0f) || std::isinf(clip.max_norm)))
     return fail(CBX_ERR_INVALID, "%s: max_norm %g is negative, NaN or infinite", me, (double)clip.max_norm);
   if (clipped && clip.skip_nonfinite != 0 && clip.skip_nonfinite != 1)
@@ -611,13 +632,16 @@ static int plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *
       return fail(CBX_ERR_INVALID, "%s: stepping replica %d: g must be non-null and 16-byte aligned", me, id);
     if (st && rmom && (!rlast[id] || !aligned16(rlast[id])))
       return fail(CBX_ERR_INVALID, "%s: stepping replica %d: replica momentum > 0 needs a 16-byte aligned last buffer", me, id);
-    if (clipped && st) {
+    if ((clipped || adaptive) && st) {
       if (!clip.slot) return fail(CBX_ERR_INVALID, "%s: stepping replica %d without a slot list", me, id);
+      if (adaptive && clip.slot[id] >= (int)p->devs[0].adaptive.size())
+        return fail(CBX_ERR_INVALID, "%s: stepping replica %d: slot %d out of range [0, %d)", me, id, clip.slot[id],
+                    (int)p->devs[0].adaptive.size());
       TRY(take_clip_slot(me, id, clip.slot[id], &slots_taken));
     }
     if (++participating > cbx::kMaxReplicas) continue;  // counted on, refused below
     const int k = a.nrep++;
-    slot_of[k] = clipped && st ? clip.slot[id] : -1;
+    slot_of[k] = (clipped || adaptive) && st ? clip.slot[id] : -1;
     a.w[k] = reinterpret_cast<cbx::v4f *>(w[id]);
     a.s[k] = reinterpret_cast<cbx::v4f *>(s[id]);
     if (st) {
@@ -649,6 +673,25 @@ static int plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *
   cbx::ClipRecordPtrs records;
   const bool clips = clipped && steps;  // nobody steps: nothing to clip
   if (clips) TRY(plan_norm_passes(p, me, a, slot_of, clip, st0, records));
+  if (adaptive && steps) {
+    // The stepping replicas' norms in one batched pass and one trust launch
+    // over their slots' scratch, then the barrier, all three on streams[0].
+    cbx::ReplicaSteps rs;
+    for (int k = 0; k < a.nrep; ++k) {
+      if (slot_of[k] < 0) continue;
+      const int j = rs.count++;
+      rs.w[j] = reinterpret_cast<const float *>(a.w[k]);
+      rs.g[j] = reinterpret_cast<const float *>(a.g[k]);
+      rs.scratch[j] = &d.adaptive[(size_t)slot_of[k]];
+      rs.rate[j] = a.rate[k];
+      rs.col[j] = k;
+    }
+    const cbx::AdaptiveParams prm = {clip.trust, clip.epsilon, weight_decay, clip.mode};
+    HIP_TRY(cbx::launch_replica_norms(rs, d.adaptive_tables, d.var_tables.mult, prm, d.rate_matrix, d.var_tables.nvars,
+                                      p->adaptive_norm_policy, st0));
+    HIP_TRY(cbx::launch_task_barrier_adaptive(a, d.var_tables, d.rate_matrix, keep, cfg, st0, p->next_timing()));
+    return copies > 0 ? 1 : 0;
+  }
   HIP_TRY(cbx::pick_task_barrier_launch(a, variables ? &d.var_tables : nullptr, clips ? &records : nullptr, keep, cfg,
                                         st0, p->next_timing()));
   return copies > 0 ? 1 : 0;
@@ -704,6 +747,22 @@ int cbx_sma_plan_step_and_optimise_clipped_variables(cbx_sma_plan *p, void *cons
   return plan_step_and_optimise(p, streams, z, last, nreplicas, replica_device, w, s, g, rlast, locked, copy, step,
                                 learning_rate, alpha, momentum, replica_momentum, weight_decay, first, flags,
                                 SeamClippedVariables, clip);
+}
+
+int cbx_sma_plan_step_and_optimise_adaptive(cbx_sma_plan *p, void *const *streams, float *const *z, float *const *last,
+                                            int nreplicas, const int *replica_device, float *const *w, float *const *s,
+                                            float *const *g, float *const *rlast, const int *locked, const int *copy,
+                                            const int *step, const float *learning_rate, const int *slot, float trust,
+                                            float epsilon, int mode, float alpha, float momentum,
+                                            float replica_momentum, float weight_decay, int first, unsigned flags) {
+  SeamClip ad;
+  ad.slot = slot;
+  ad.trust = trust;
+  ad.epsilon = epsilon;
+  ad.mode = mode;
+  return plan_step_and_optimise(p, streams, z, last, nreplicas, replica_device, w, s, g, rlast, locked, copy, step,
+                                learning_rate, alpha, momentum, replica_momentum, weight_decay, first, flags,
+                                SeamAdaptive, ad);
 }
 
 // The task steps of kernels/optimisers/synchronouseamsgd.cu of every stepping
@@ -1141,6 +1200,7 @@ int cbx_sma_plan_set_variables(cbx_sma_plan *p, const long long *var_elements, c
                                    multipliers, (uint32_t)nvars));
     // the adaptive tables belong to the list that has just been replaced
     cbx::adaptive_tables_free(d.adaptive_tables);
+    cbx::rate_matrix_free(d.rate_matrix);
     for (cbx::AdaptiveScratch &as : d.adaptive) cbx::adaptive_scratch_free(as);
     d.adaptive.clear();
   }
@@ -1167,6 +1227,7 @@ int cbx_sma_plan_set_adaptive(cbx_sma_plan *p, const unsigned char *enable, int 
     for (cbx::AdaptiveScratch &as : d.adaptive) cbx::adaptive_scratch_free(as);
     d.adaptive.assign((size_t)slots, cbx::AdaptiveScratch());
     HIP_TRY(cbx::adaptive_tables_upload(d.adaptive_tables, pieces, enable));
+    HIP_TRY(cbx::rate_matrix_alloc(d.rate_matrix, d.adaptive_tables));
     for (cbx::AdaptiveScratch &as : d.adaptive) HIP_TRY(cbx::adaptive_scratch_alloc(as, d.adaptive_tables));
   }
   return CBX_OK;

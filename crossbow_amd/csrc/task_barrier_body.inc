@@ -1,4 +1,4 @@
-// task_barrier_body.inc -- the body of the four fused task-step barrier
+// task_barrier_body.inc -- the body of the five fused task-step barrier
 // kernels, included inside each of them behind its step policy `step`
 // (task_barrier_step.h).  It is shared as text and not as a function: behind a
 // call, even an inlined one, the compiler schedules the kernels differently,
@@ -50,6 +50,7 @@
     // through scalar loads, issued with the trip's first float4 loads.
     [[maybe_unused]] uint32_t ch, e[U];
     [[maybe_unused]] v4f mv[U];
+    [[maybe_unused]] uint32_t vr[U][4];  // adaptive, a mixed chunk: the matrix row of each of the lane's four floats
     if constexpr (STEP::kPerVariable) {
       ch = (uint32_t)__builtin_amdgcn_readfirstlane((int)(base >> 6));
 #pragma unroll
@@ -100,7 +101,33 @@
       __builtin_amdgcn_sched_barrier(0);
       // byte offsets of the chunk's stores
       [[maybe_unused]] uint32_t so[U];
-      if constexpr (STEP::kPerVariable) {
+      [[maybe_unused]] float rt[U][RR];  // adaptive, a uniform chunk: the finished rates of this replica chunk
+      if constexpr (STEP::kAdaptive) {
+        // The finished rates (rate_i * m_v) * t_iv of this replica chunk, where
+        // the multiplier is loaded below: behind the chunk's float4 loads.  A
+        // uniform chunk takes the RR consecutive floats of its variable's row
+        // from column c in one scalar load, once per replica chunk, so the
+        // runtime-chunked form reads the next 8 columns each time round.  In a
+        // chunk with a boundary inside each lane finds the row of each of its
+        // four floats once per trip and gathers the rates in the replica loop:
+        // RR x 4 of them per lane would not fit beside the streams.
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const uint32_t v0 = e[u] >> 1;
+          if ((e[u] & 1u) == 0u) {  // wave-uniform
+            uniform_rates<RR>(step.matrix + v0 * kMaxReplicas, c, rt[u]);
+          } else if (R > 0 || c == 0) {
+            const uint32_t f = (ch + u) * kOptChunk + lane * 4u;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) vr[u][k] = variable_of(step.bounds, step.nvars, v0, f + k) * kMaxReplicas;
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {  // the offsets, made opaque as below
+          so[u] = (base + u * 64u) * 16u;
+          asm volatile("" : "+v"(so[u]));
+        }
+      } else if constexpr (STEP::kPerVariable) {
         // The multipliers, once per trip and behind the first replica chunk's
         // loads: the table entry is not waited for ahead of them.  In a chunk
         // with a boundary inside, each lane finds the variable of each of its
@@ -148,7 +175,16 @@
             // r_iv is a vector multiply of the (scalar) rate_i by the lane's four
             // multipliers: the same bits as a scalar multiply, and no branch here
             v4f rv = rate;
-            if constexpr (STEP::kPerVariable) rv = rate * mv[u];
+            if constexpr (STEP::kAdaptive) {
+              if ((e[u] & 1u) == 0u) {
+                rv = rt[u][r];
+              } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) rv[k] = step.matrix[vr[u][k] + (uint32_t)(c + r)];
+              }
+            } else if constexpr (STEP::kPerVariable) {
+              rv = rate * mv[u];
+            }
             v4f gv = y[u][r];
             if constexpr (STEP::kClips) gv = scale * y[u][r];
             if constexpr (WD) gv = vfma(wd, sv, gv);

@@ -1,6 +1,7 @@
-// task_barrier_launch.h -- the host side the four fused task-step barrier
+// task_barrier_launch.h -- the host side the five fused task-step barrier
 // launches share (launch_task_barrier, launch_task_barrier_variables,
-// launch_task_barrier_clipped, launch_task_barrier_clipped_variables): the
+// launch_task_barrier_clipped, launch_task_barrier_clipped_variables,
+// launch_task_barrier_adaptive): the
 // launch check, the grid, the ladders from the run-time arguments to one kernel
 // instantiation, and the checks of the tables and the records.
 //

@@ -1,7 +1,7 @@
-// task_barrier_step.h -- what the four fused task-step barrier kernels differ
+// task_barrier_step.h -- what the five fused task-step barrier kernels differ
 // in (task_barrier_kernels.hip, task_barrier_variables_kernels.hip,
-// task_barrier_clipped_kernels.hip, task_barrier_clipped_variables_kernels.hip),
-// and the element-wise tail they share.  Device code only; the bulk of the
+// task_barrier_clipped_kernels.hip, task_barrier_clipped_variables_kernels.hip,
+// task_barrier_adaptive_kernels.hip), and the element-wise tail they share.  Device code only; the bulk of the
 // kernels is task_barrier_body.inc.
 //
 // A step policy is a mode's two constants and the kernel parameters it has
@@ -9,7 +9,9 @@
 // `if constexpr` on its constants, so an instantiation holds nothing of a mode
 // it is not.  The kernel that is both (a learning rate per variable and
 // clipped) is the fourth policy, with both constants set and both sets of
-// members.
+// members.  The fifth, with layer-wise adaptive rates, is a per-variable
+// policy whose rate is finished before the launch: kAdaptive, read only under
+// `if constexpr`, false for the other four.
 #pragma once
 
 #include <cstddef>
@@ -23,7 +25,7 @@ namespace cbx {
 
 // Plain: replica i steps with a.rate[i] (sma.cu:3-100).
 struct PlainStep {
-  static constexpr bool kPerVariable = false, kClips = false;
+  static constexpr bool kPerVariable = false, kClips = false, kAdaptive = false;
 };
 
 // A learning rate per variable: r_iv = a.rate[i] * mult[v], one fp32 multiply
@@ -32,7 +34,7 @@ struct PlainStep {
 // `const __restrict__`, so the entry and the multiplier of a uniform chunk
 // arrive through scalar loads.
 struct VariablesStep {
-  static constexpr bool kPerVariable = true, kClips = false;
+  static constexpr bool kPerVariable = true, kClips = false, kAdaptive = false;
   const uint32_t *__restrict__ chunks;
   const uint32_t *__restrict__ bounds;
   const float *__restrict__ mult;
@@ -45,7 +47,7 @@ struct VariablesStep {
 // entry whose replica only joins is loaded and not used, so it holds some valid
 // record as well (launch_task_barrier_clipped).
 struct ClippedStep {
-  static constexpr bool kPerVariable = false, kClips = true;
+  static constexpr bool kPerVariable = false, kClips = true, kAdaptive = false;
   const ClipRecordPtrs &rec;
 };
 
@@ -53,12 +55,28 @@ struct ClippedStep {
 // * mult[v]; the skip and the kept g are ClippedStep's
 // (launch_sma_optimise_variables_clipped per replica, clip_internal.h).
 struct ClippedVariablesStep {
-  static constexpr bool kPerVariable = true, kClips = true;
+  static constexpr bool kPerVariable = true, kClips = true, kAdaptive = false;
   const uint32_t *__restrict__ chunks;
   const uint32_t *__restrict__ bounds;
   const float *__restrict__ mult;
   uint32_t nvars;
   const ClipRecordPtrs &rec;
+};
+
+// Layer-wise adaptive rates: r_iv = (a.rate[i] * mult[v]) * trust_i[v], two fp32
+// multiplies made by replica_trust_kernel (task_barrier_adaptive_kernels.hip)
+// before the launch.  matrix[v * kMaxReplicas + k] is the finished rate of
+// participating replica k on variable v: variable-major, so the rates of the
+// replicas of one replica chunk on a uniform 256-float chunk are consecutive
+// floats behind a wave-uniform address, one scalar load (uniform_rates).  A
+// column whose replica only joins is loaded and not used.  No mult: the barrier
+// kernel multiplies nothing.
+struct AdaptiveStep {
+  static constexpr bool kPerVariable = true, kClips = false, kAdaptive = true;
+  const uint32_t *__restrict__ chunks;
+  const uint32_t *__restrict__ bounds;
+  uint32_t nvars;
+  const float *__restrict__ matrix;
 };
 
 // The policy S, named through a template parameter of the kernel: `if
@@ -81,6 +99,29 @@ typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ v2u record_words(const ClipRecord *rec) {
   typedef const v2u __attribute__((address_space(4))) * cptr;
   return *(cptr)(reinterpret_cast<uintptr_t>(rec) + 16u);
+}
+
+// N consecutive rates of one row of AdaptiveStep's matrix behind a wave-uniform
+// address: one scalar load of 1, 2, 4 or 8 dwords from the constant address
+// space (the matrix was written by an earlier kernel on the stream and is not
+// written here).  row is 256-byte aligned and col a multiple of kChunk, so the
+// widest load is 32-byte aligned and ends inside the row of kMaxReplicas
+// floats whatever N is.
+template <int N>
+__device__ __forceinline__ void uniform_rates(const float *row, int col, float (&out)[N]) {
+  static_assert(N >= 1 && N <= 8 && kMaxReplicas % 8 == 0, "one load of at most 8 dwords inside a row");
+  constexpr int W = N > 4 ? 8 : N > 2 ? 4 : N;
+  const uintptr_t at = reinterpret_cast<uintptr_t>(row) + (uintptr_t)(uint32_t)col * 4u;
+  if constexpr (W == 1) {
+    typedef const float __attribute__((address_space(4))) * cptr;
+    out[0] = *(cptr)at;
+  } else {
+    typedef float vw __attribute__((ext_vector_type(W)));
+    typedef const vw __attribute__((address_space(4))) * cptr;
+    const vw v = *(cptr)at;
+#pragma unroll
+    for (int j = 0; j < N; ++j) out[j] = v[j];
+  }
 }
 
 // skip ? kept : made, word by word (v_cndmask) on integer views: no arithmetic
@@ -113,10 +154,14 @@ template <bool MOM, bool BMOM, bool WD, bool KEEP, class STEP>
 __device__ __forceinline__ void task_barrier_tail_elem(const TaskBarrierArgs &a, const STEP &step) {
   const int64_t i = a.tail_lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.tail_hi) return;
-  [[maybe_unused]] float m;  // the float's own multiplier
+  [[maybe_unused]] float m;      // the float's own multiplier
+  [[maybe_unused]] uint32_t vi;  // adaptive: the float's own row of the rate matrix
   if constexpr (STEP::kPerVariable) {
     const uint32_t en = step.chunks[(uint32_t)i / kOptChunk];
-    m = step.mult[(en & 1u) ? variable_of(step.bounds, step.nvars, en >> 1, (uint32_t)i) : (en >> 1)];
+    if constexpr (STEP::kAdaptive)
+      vi = ((en & 1u) ? variable_of(step.bounds, step.nvars, en >> 1, (uint32_t)i) : (en >> 1)) * kMaxReplicas;
+    else
+      m = step.mult[(en & 1u) ? variable_of(step.bounds, step.nvars, en >> 1, (uint32_t)i) : (en >> 1)];
   }
   float *z = reinterpret_cast<float *>(a.z);
   float z0 = z[i];
@@ -151,7 +196,8 @@ __device__ __forceinline__ void task_barrier_tail_elem(const TaskBarrierArgs &a,
           [[maybe_unused]] bool skip = false;
           if constexpr (STEP::kClips) skip = (sf[r][1] & kClipSkipped) != 0u;
           float rate = a.rate[c + r];
-          if constexpr (STEP::kPerVariable) rate = a.rate[c + r] * m;  // model.c:159-177
+          if constexpr (STEP::kAdaptive) rate = step.matrix[vi + (uint32_t)(c + r)];  // (rate_i * m_v) * t_iv
+          else if constexpr (STEP::kPerVariable) rate = a.rate[c + r] * m;              // model.c:159-177
           float gv = y[r];
           if constexpr (STEP::kClips) gv = __uint_as_float(sf[r][0]) * y[r];
           if constexpr (WD) gv = fmaf(a.wd, sv, gv);  // sma.cu:24-31

@@ -132,6 +132,23 @@ class SmaPlan:
                                        (_ints(slots) if slots is not None else None, ctypes.c_float(max_norm),
                                         1 if skip_nonfinite else 0))
 
+    def step_and_optimise_adaptive(self, streams, z, last, replicas, alpha: float, momentum: float,
+                                   replica_momentum: float, weight_decay: float, first: int = 0, flags: int = 0,
+                                   slots: Optional[Sequence[int]] = None, trust: float = 0.0, epsilon: float = 0.0,
+                                   mode: int = 0) -> int:
+        """``step_and_optimise`` with the layer-wise adaptive step of
+        ``optimise_adaptive`` (``cbx_sma_plan_step_and_optimise_adaptive``;
+        after ``set_variables`` and ``set_adaptive``): the stepping replicas'
+        norms run as two batched launches on ``streams[0]`` over the scratch of
+        ``slots[id]``, then variable v of stepping replica id steps at
+        ``(learning_rate * multipliers[v]) * trust ratio`` inside the barrier's
+        launch.  Two stepping replicas take two slots; ``adaptive_stats`` reads
+        a slot's records afterwards.  Otherwise the same arguments."""
+        return self._step_and_optimise("cbx_sma_plan_step_and_optimise_adaptive", streams, z, last, replicas, alpha,
+                                       momentum, replica_momentum, weight_decay, first, flags,
+                                       (_ints(slots) if slots is not None else None, ctypes.c_float(trust),
+                                        ctypes.c_float(epsilon), mode))
+
     def _step_and_optimise(self, name, streams, z, last, replicas, alpha, momentum, replica_momentum, weight_decay,
                            first, flags, clip=()) -> int:
         rate = (ctypes.c_float * max(1, len(replicas)))(*[float(r[8]) for r in replicas])

@@ -269,6 +269,18 @@ class TheGPU:
         return self._step_and_synchronise(self._L.cbx_step_and_synchronise_clipped_variables, first, clock, autotune,
                                           tasks, streams, flags)
 
+    def step_and_synchronise_adaptive(self, first: int, clock: int, autotune: int, tasks: Sequence[int],
+                                      streams: Optional[Sequence[Optional[int]]] = None, flags: int = 0) -> int:
+        """``cbx_step_and_synchronise_adaptive``: ``step_and_synchronise`` with
+        layer-wise adaptive rates on (``set_adaptive_rate``), which every other
+        fused call refuses: the stepping replicas' norms run as two batched
+        launches on the sync stream, and the step with each variable's trust
+        ratio inside the barrier's launch.  ``replica_adaptive_stats`` reads
+        the records afterwards.  Same arguments; with the rates off it is
+        ``step_and_synchronise`` or ``step_and_synchronise_variables``."""
+        return self._step_and_synchronise(self._L.cbx_step_and_synchronise_adaptive, first, clock, autotune, tasks,
+                                          streams, flags)
+
     def step_and_synchronise_elastic(self, first: int, clock: int, autotune: int, tasks: Sequence[int],
                                      streams: Optional[Sequence[Optional[int]]] = None, flags: int = 0) -> int:
         """``cbx_step_and_synchronise_elastic``: ``step_and_synchronise`` for

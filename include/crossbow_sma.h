@@ -361,6 +361,44 @@ int cbx_step_and_synchronise_clipped (cbx_context *ctx, int first, int clock, in
  * and no record is touched.                                                 */
 int cbx_step_and_synchronise_clipped_variables (cbx_context *ctx, int first, int clock, int autotune,
                                                 const int *tasks, void *const *streams, unsigned flags);
+/* cbx_step_and_synchronise with layer-wise adaptive rates on
+ * (cbx_set_adaptive_rate), which every other fused call refuses.  One GPU and
+ * the SMA barrier only: update model SMA (7), or SYNCHRONOUSEAMSGD (3) with
+ * elastic averaging off.  Same parameters.
+ *
+ * Behind the deferred waits for the callers' streams the call enqueues three
+ * launches on the device's sync stream: one two-buffer pass over w and g of
+ * every stepping replica at once, one launch with a wave per (variable,
+ * stepping replica) that leaves the replica's cbx_adaptive_stats records and
+ * its trust table exactly as cbx_replica_optimise leaves them and the finished
+ * rates in a matrix on the device, and the barrier's launch, in which stepping
+ * replica i steps variable v with
+ *   r_iv = (rate_i * m_v) * t_iv         rate_i = -lr_i, two fp32 multiplies in that order
+ * and otherwise cbx_step_and_synchronise_variables' arithmetic.  The norms are
+ * taken over the raw g and over w as they stand before the step, over exactly
+ * the model's floats; m_v is 1 unless cbx_set_variable_learning_rates is on with
+ * an irregular variable; the weight decay in the ratio is the stepping
+ * replicas' common value.
+ *
+ * The contract.  With flags == 0, z, the base `last`, every replica's w, s, g
+ * and `last`, every stepping replica's records (cbx_replica_adaptive_stats) and
+ * every piece of host state are left bit for bit as after
+ *   cbx_replica_optimise (ctx, id, tasks[id], streams[id])  (adaptive rates on)
+ *                                     for every id with tasks[id] >= 0, in id order,
+ *   cbx_synchronise (ctx, first, clock, autotune, 0).
+ * With CBX_STEP_DISCARD_TASK_OUTPUTS, s_i and g_i of the stepping replicas are
+ * not written.
+ *
+ * With adaptive rates off the call is cbx_step_and_synchronise_variables (or,
+ * without per-variable rates, cbx_step_and_synchronise): the same kernel, the
+ * same bits.  When no replica steps there is no norm launch and no record is
+ * touched.  CBX_ERR_UNSUPPORTED, before any side effect: gradient clipping also
+ * on (the two are not composed); elastic averaging or another update model;
+ * a model without variable ranges or whose padded length has no chunk table;
+ * and everything cbx_step_and_synchronise refuses.  CBX_ERR_STATE: a stepping
+ * replica without adaptive-rate scratch.                                     */
+int cbx_step_and_synchronise_adaptive (cbx_context *ctx, int first, int clock, int autotune,
+                                       const int *tasks, void *const *streams, unsigned flags);
 /* The pending task steps of the locked replicas and the one-GPU
  * elastic-averaging barrier in one launch: cbx_step_and_synchronise for EA-SGD
  * (update model SYNCHRONOUSEAMSGD (3) with cbx_set_elastic_average on; the
@@ -1443,6 +1481,36 @@ int cbx_sma_plan_step_and_optimise_clipped_variables (cbx_sma_plan *plan, void *
                                                       const int *slot, float max_norm, int skip_nonfinite,
                                                       float alpha, float momentum, float replica_momentum,
                                                       float weight_decay, int first, unsigned flags);
+/* cbx_sma_plan_step_and_optimise_variables with layer-wise adaptive rates:
+ * cbx_step_and_synchronise_adaptive over caller-owned buffers.  CBX_ERR_STATE
+ * without cbx_sma_plan_set_variables and cbx_sma_plan_set_adaptive, before any
+ * other check but the NULL plan.  slot[id] is the adaptive scratch of stepping
+ * replica id (cbx_sma_plan_adaptive_stats reads its records afterwards): a
+ * NULL list with a stepping replica, a slot outside the range
+ * cbx_sma_plan_set_adaptive made, and two stepping replicas in one slot are
+ * CBX_ERR_INVALID.  trust, epsilon and mode are
+ * cbx_sma_plan_optimise_adaptive's, with its checks.  The three launches go to
+ * streams[0]; the plan queues no wait.  With flags == 0 every buffer and every
+ * slot's records are left bit for bit as after
+ *   cbx_sma_plan_optimise_adaptive (plan, 0, slot[id], streams[0], w[id], g[id],
+ *       rlast[id], s[id], learning_rate[id], replica_momentum, weight_decay,
+ *       trust, epsilon, mode)            for every id with step[id] != 0, in id order,
+ *   cbx_sma_plan_step (plan, streams, z, last, nreplicas, replica_device, w, s,
+ *       locked, copy, alpha, momentum, first);
+ * with CBX_STEP_DISCARD_TASK_OUTPUTS, s[id] and g[id] of the stepping replicas
+ * are not written.  When no replica steps the call is
+ * cbx_sma_plan_step_and_optimise_variables'.  Nothing at or past `elements` is
+ * read or written.                                                          */
+int cbx_sma_plan_step_and_optimise_adaptive (cbx_sma_plan *plan, void *const *streams,
+                                             float *const *z, float *const *last,
+                                             int nreplicas, const int *replica_device,
+                                             float *const *w, float *const *s, float *const *g,
+                                             float *const *rlast,
+                                             const int *locked, const int *copy, const int *step,
+                                             const float *learning_rate,
+                                             const int *slot, float trust, float epsilon, int mode,
+                                             float alpha, float momentum, float replica_momentum,
+                                             float weight_decay, int first, unsigned flags);
 /* The statistics reduction of cbx_model_stats over caller-owned buffers of
  * exactly the plan's `elements` floats on the plan's device k (where a
  * Crossbow build would checksum, databuffer.c:141-162): `ref` against
