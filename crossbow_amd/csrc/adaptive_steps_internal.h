@@ -1,7 +1,9 @@
 // adaptive_steps_internal.h -- the replicas' pending task steps with layer-wise
 // adaptive rates (LARS, LARC) fused into the one-GPU SMA barrier
 // (task_barrier_adaptive_kernels.hip; cbx_step_and_synchronise_adaptive,
-// cbx_sma_plan_step_and_optimise_adaptive).  Not part of the C-ABI; see
+// cbx_sma_plan_step_and_optimise_adaptive) and into the elastic-averaging one
+// (task_elastic_adaptive_kernels.hip; cbx_step_and_synchronise_elastic_adaptive,
+// cbx_ea_plan_step_and_optimise_adaptive).  Not part of the C-ABI; see
 // include/crossbow_sma.h for the semantics and adaptive_internal.h for the
 // tables, the scratch and the records, which are the replica step's.
 #pragma once
@@ -56,6 +58,17 @@ hipError_t launch_replica_norms(const ReplicaSteps &rs, const AdaptiveTables &t,
 // launch_task_barrier_variables (t.mult is not read); m.rows >= t.nvars.  At
 // least one replica steps.  The compiled forms are that launch's.
 hipError_t launch_task_barrier_adaptive(const TaskBarrierArgs &a, const VarTables &t, const RateMatrix &m,
+                                        bool keep_task_outputs, const LaunchConfig &cfg, hipStream_t stream,
+                                        Timing tm = {});
+
+// launch_task_elastic_variables with the rates of `m` in place of
+// a.rate[k] * t.mult[v] (task_elastic_adaptive_kernels.hip,
+// libcrossbow_sma_elastic_adaptive.so): per stepping replica
+// launch_sma_optimise_adaptive's bits, then the elastic-averaging barrier's.
+// `t`, `m` and the stepping replica as for launch_task_barrier_adaptive; `m` is
+// what launch_replica_norms left on the same stream.  The compiled forms are
+// launch_task_elastic's.
+hipError_t launch_task_elastic_adaptive(const TaskBarrierArgs &a, const VarTables &t, const RateMatrix &m,
                                         bool keep_task_outputs, const LaunchConfig &cfg, hipStream_t stream,
                                         Timing tm = {});
 

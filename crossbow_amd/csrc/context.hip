@@ -761,8 +761,9 @@ static int check_fused_call(cbx_context *c, const char *me, int first, const int
   if (flags & ~CBX_STEP_DISCARD_TASK_OUTPUTS) return fail(CBX_ERR_INVALID, "%s: unknown flag bits 0x%x", me, flags);
   if (c->adaptive_on() && !adaptive_ok)
     return fail(CBX_ERR_UNSUPPORTED, "%s: layer-wise adaptive rates are on (cbx_set_adaptive_rate); the adaptive step "
-                "needs its norm pass first and is fused into the one-GPU SMA barrier only, use "
-                "cbx_step_and_synchronise_adaptive, or cbx_replica_optimise and cbx_synchronise", me);
+                "needs its norm pass first and is fused into the one-GPU SMA and elastic-averaging barriers only, use "
+                "cbx_step_and_synchronise_adaptive or cbx_step_and_synchronise_elastic_adaptive, or "
+                "cbx_replica_optimise and cbx_synchronise", me);
   const int size = c->size;
   for (int id = 0; id < size; ++id) {
     if (tasks[id] < -1) return fail(CBX_ERR_INVALID, "%s: tasks[%d] = %d is neither a task number nor -1", me, id, tasks[id]);
@@ -914,7 +915,8 @@ static int step_and_synchronise(cbx_context *c, int first, int clock, int autotu
   const bool adaptive = c->adaptive_on();  // only FusedAdaptive comes this far with them on
   if (type == CBX_UPDATE_SYNCHRONOUSEAMSGD && c->elastic_average)
     return fail(CBX_ERR_UNSUPPORTED, "%s: elastic averaging is on (cbx_set_elastic_average); only the SMA barrier is "
-                "fused%s", me, adaptive ? ", use cbx_replica_optimise and cbx_synchronise" : "");
+                "fused%s", me, adaptive ? " here, use cbx_step_and_synchronise_elastic_adaptive, or cbx_replica_optimise and "
+                "cbx_synchronise" : "");
   if (type != CBX_UPDATE_SMA && type != CBX_UPDATE_SYNCHRONOUSEAMSGD)
     return fail(CBX_ERR_UNSUPPORTED, "%s: update model %d; only SMA (7) and SYNCHRONOUSEAMSGD (3) are fused%s", me, type,
                 adaptive ? ", and only they have an adaptive step: turn the rates off (cbx_set_adaptive_rate)" : "");
@@ -1054,28 +1056,52 @@ int cbx_step_and_synchronise_adaptive(cbx_context *c, int first, int clock, int 
 // (synchronouseamsgd.c:42-90 has no Phase D): a flag that a rate query of this
 // call raises stays raised, as after the two calls.  It ends as
 // averaging_step's fused form does.
-// cbx_step_and_synchronise_elastic (`policies` false) refuses gradient clipping
+// cbx_step_and_synchronise_elastic (ElasticPlain) refuses gradient clipping
 // and per-variable rates.  cbx_step_and_synchronise_elastic_clipped_variables
-// refuses neither, as FusedClippedVariables above: with clipping on and a
-// stepping replica it runs the norm passes where the SMA call places them
-// (launch_fused_norms), and the kernel is the one of what is on
+// (ElasticPolicies) refuses neither, as FusedClippedVariables above: with
+// clipping on and a stepping replica it runs the norm passes where the SMA call
+// places them (launch_fused_norms), and the kernel is the one of what is on
 // (libcrossbow_sma_elastic_policies.so); with both off, or clipping alone and
 // nobody stepping, it is the plain call's launch.
+// cbx_step_and_synchronise_elastic_adaptive (ElasticAdaptive) is the one
+// elastic call that passes with layer-wise adaptive rates on, as FusedAdaptive
+// above: behind the callers' deferred waits it puts every stepping replica's
+// norms in two batched launches on the sync stream (launch_replica_norms) and
+// then the kernel that takes its rates from the rate matrix
+// (task_elastic_adaptive_kernels.hip); with the rates off it launches what
+// ElasticPlain or ElasticPolicies launches, and with nobody stepping the plain
+// barrier.
+enum ElasticMode { ElasticPlain, ElasticPolicies, ElasticAdaptive };
+
 static int step_and_synchronise_elastic(cbx_context *c, int first, int clock, int autotune, const int *tasks,
-                                        void *const *streams, unsigned flags, bool policies) {
+                                        void *const *streams, unsigned flags, ElasticMode mode) {
   const char *other = "cbx_step_and_synchronise_elastic_clipped_variables";
-  const char *me = policies ? other : "cbx_step_and_synchronise_elastic";
+  const char *me = mode == ElasticAdaptive   ? "cbx_step_and_synchronise_elastic_adaptive"
+                   : mode == ElasticPolicies ? other
+                                             : "cbx_step_and_synchronise_elastic";
+  const bool policies = mode != ElasticPlain;
   TraceRange trace(me);
-  TRY(check_fused_call(c, me, first, tasks, flags));
+  TRY(check_fused_call(c, me, first, tasks, flags, nullptr, mode == ElasticAdaptive));
   const int type = c->model.type;
+  const bool adaptive = c->adaptive_on();  // only ElasticAdaptive comes this far with them on
   if ((type == CBX_UPDATE_SMA || type == CBX_UPDATE_SYNCHRONOUSEAMSGD) && !c->elastic_average)
     return fail(CBX_ERR_UNSUPPORTED, "%s: elastic averaging is off (cbx_set_elastic_average); the SMA barrier takes "
-                "cbx_step_and_synchronise", me);
+                "cbx_step_and_synchronise%s", me, adaptive ? "_adaptive" : "");
   if (type != CBX_UPDATE_SYNCHRONOUSEAMSGD)
     return fail(CBX_ERR_UNSUPPORTED, "%s: update model %d; only SYNCHRONOUSEAMSGD (3) with elastic averaging on is fused "
-                "here", me, type);
+                "here%s", me, type,
+                adaptive ? ", and only SMA (7) and it have an adaptive step: turn the rates off (cbx_set_adaptive_rate)" : "");
   const bool clip = c->clip_on();
   const bool per_variable = c->variable_rates && c->model.conf.irregular > 0;
+  if (adaptive && clip)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: layer-wise adaptive rates and gradient clipping are both on: the two are not "
+                "composed yet; turn one off (cbx_set_gradient_clip or cbx_set_adaptive_rate)", me);
+  if (adaptive && !c->var_refusal.empty())
+    return fail(CBX_ERR_UNSUPPORTED, "%s with layer-wise adaptive rates (cbx_set_adaptive_rate): %s; turn them off for "
+                "cbx_step_and_synchronise_elastic", me, c->var_refusal.c_str());
+  if (adaptive && !c->devs[0].var_tables_padded.chunks)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: the padded model is too large for the chunk table; use cbx_replica_optimise "
+                "and cbx_synchronise", me);
   if (clip && !policies)
     return fail(CBX_ERR_UNSUPPORTED, "%s: gradient clipping is on; the clipped step needs its norm pass first, use %s, "
                 "or cbx_replica_optimise and cbx_synchronise", me, other);
@@ -1089,12 +1115,21 @@ static int step_and_synchronise_elastic(cbx_context *c, int first, int clock, in
     return fail(CBX_ERR_UNSUPPORTED, "%s: the padded model is too large for the chunk table", me);
   const SolverConf *ref = nullptr;  // the first stepping replica's configuration (null: nobody steps)
   TRY(check_stepping_replicas(c, me, first, tasks, clip, &ref));
+  const bool adaptive_steps = adaptive && ref != nullptr;  // nobody steps: the plain barrier, no norm launch
+  if (adaptive_steps) {
+    for (int id : d.replicas)
+      if (id >= first && c->locked[id] && tasks[id] >= 0 && !c->replicas[id]->adaptive.dev)
+        return fail(CBX_ERR_STATE, "replica %d has no adaptive-rate scratch", id);
+    if (!d.adaptive_tables.dev || !d.rate_matrix.dev || d.adaptive_tables.nvars != d.var_tables.nvars)
+      return fail(CBX_ERR_STATE, "%s: device %d has no adaptive-rate tables", me, d.g);
+  }
 
   std::vector<float> lr((size_t)c->size, 0.0f);
   TRY(query_rates(c, tasks, lr));
 
   FusedSteps f;
   cbx::TaskBarrierArgs &a = f.a;
+  cbx::ReplicaSteps rs;  // the stepping replicas of an adaptive call, id order
   int k = 0;
   for (int id : d.replicas) {  // increasing id order, synchronouseamsgd.c:46
     if (id < first || !c->locked[id]) continue;
@@ -1103,6 +1138,14 @@ static int step_and_synchronise_elastic(cbx_context *c, int first, int clock, in
     if (tasks[id] >= 0) {
       a.s[k] = reinterpret_cast<cbx::v4f *>(replica_dev(d, r, CBX_BUF_DIFF));
       f.step(d, r, k, lr[(size_t)id], streams ? streams[id] : nullptr, clip);
+      if (adaptive_steps) {
+        const int j = rs.count++;
+        rs.w[j] = reinterpret_cast<const float *>(a.w[k]);
+        rs.g[j] = reinterpret_cast<const float *>(a.g[k]);
+        rs.scratch[j] = &r.adaptive;
+        rs.rate[j] = a.rate[k];
+        rs.col[j] = k;
+      }
     }
     ++k;
   }
@@ -1123,9 +1166,22 @@ static int step_and_synchronise_elastic(cbx_context *c, int first, int clock, in
   cbx::LaunchConfig cfg = c->task_barrier_cfg;
   cfg.num_cus = d.num_cus;
   const bool keep = (flags & CBX_STEP_DISCARD_TASK_OUTPUTS) == 0;
-  const cbx::Timing tm = {step_start_event(c, d, 0), step_stop_event(c, d, EV_A)};
-  HIP_TRY(cbx::pick_task_elastic_launch(a, per_variable ? &d.var_tables_padded : nullptr,
-                                        f.norms.empty() ? nullptr : &f.records, keep, cfg, d.stream, tm));
+  if (adaptive_steps) {
+    // Every stepping replica's norms in one batched pass and one trust launch,
+    // on the sync stream behind the waits, as FusedAdaptive places them: in
+    // order on this stream they are behind the previous barrier's use of every
+    // record, trust table and matrix column.  The pad of the buffers is the
+    // matrix's last row (ratio and multiplier 1).
+    const cbx::AdaptiveParams prm = {c->adaptive_trust, c->adaptive_epsilon, ref->weightDecay, c->adaptive_mode};
+    HIP_TRY(cbx::launch_replica_norms(rs, d.adaptive_tables, per_variable ? d.var_tables.mult : d.adaptive_tables.ones(),
+                                      prm, d.rate_matrix, d.var_tables_padded.nvars, c->adaptive_norm_policy, d.stream));
+  }
+  const cbx::Timing tm = {step_start_event(c, d, 0), step_stop_event(c, d, EV_A)};  // the barrier's own start marker
+  if (adaptive_steps)
+    HIP_TRY(cbx::launch_task_elastic_adaptive(a, d.var_tables_padded, d.rate_matrix, keep, cfg, d.stream, tm));
+  else
+    HIP_TRY(cbx::pick_task_elastic_launch(a, per_variable ? &d.var_tables_padded : nullptr,
+                                          f.norms.empty() ? nullptr : &f.records, keep, cfg, d.stream, tm));
   close_fused_step(c, d);  // the ring slot, cross_valid = false: averaging_step's fused form
   TRY(finish_step(c));
   return finish_barrier(c, clock, autotune);
@@ -1133,12 +1189,17 @@ static int step_and_synchronise_elastic(cbx_context *c, int first, int clock, in
 
 int cbx_step_and_synchronise_elastic(cbx_context *c, int first, int clock, int autotune, const int *tasks,
                                      void *const *streams, unsigned flags) {
-  return step_and_synchronise_elastic(c, first, clock, autotune, tasks, streams, flags, false);
+  return step_and_synchronise_elastic(c, first, clock, autotune, tasks, streams, flags, ElasticPlain);
 }
 
 int cbx_step_and_synchronise_elastic_clipped_variables(cbx_context *c, int first, int clock, int autotune,
                                                        const int *tasks, void *const *streams, unsigned flags) {
-  return step_and_synchronise_elastic(c, first, clock, autotune, tasks, streams, flags, true);
+  return step_and_synchronise_elastic(c, first, clock, autotune, tasks, streams, flags, ElasticPolicies);
+}
+
+int cbx_step_and_synchronise_elastic_adaptive(cbx_context *c, int first, int clock, int autotune, const int *tasks,
+                                              void *const *streams, unsigned flags) {
+  return step_and_synchronise_elastic(c, first, clock, autotune, tasks, streams, flags, ElasticAdaptive);
 }
 
 // The pending task steps of the locked replicas and the one-GPU synchronous-SGD

@@ -780,19 +780,37 @@ int cbx_sma_plan_step_and_optimise_adaptive(cbx_sma_plan *p, void *const *stream
 // the plan's variable table.  The kernel is the one of what is on
 // (libcrossbow_sma_elastic_policies.so); with both off, or clipping alone and
 // nobody stepping, it is the plain call's launch.
+// cbx_ea_plan_step_and_optimise_adaptive (`adaptive`): the stepping replicas'
+// norms over their slots' scratch in two batched launches on streams[0], as
+// SeamAdaptive above has them, then the kernel that takes its rates from the
+// plan's rate matrix (task_elastic_adaptive_kernels.hip); when nobody steps,
+// the per-variable launch.  clip.slot is then the adaptive call's slot list.
 static int ea_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *const *z, int nreplicas,
                                      const int *replica_device, float *const *w, float *const *s, float *const *g,
                                      float *const *rlast, const int *locked, const int *step,
                                      const float *learning_rate, float alpha, float replica_momentum,
                                      float weight_decay, int first, unsigned flags, bool policies,
-                                     const SeamClip &clip = SeamClip(), int use_variables = 0) {
-  const char *me = policies ? "cbx_ea_plan_step_and_optimise_clipped_variables" : "cbx_ea_plan_step_and_optimise";
-  const bool clipped = clip.slot != nullptr, variables = use_variables == 1;
+                                     const SeamClip &clip = SeamClip(), int use_variables = 0, bool adaptive = false) {
+  const char *me = adaptive   ? "cbx_ea_plan_step_and_optimise_adaptive"
+                   : policies ? "cbx_ea_plan_step_and_optimise_clipped_variables"
+                              : "cbx_ea_plan_step_and_optimise";
+  const bool clipped = !adaptive && clip.slot != nullptr, variables = use_variables == 1;
   TraceRange trace(me);
   if (!p) return fail(CBX_ERR_INVALID, "null plan");
   if (use_variables != 0 && use_variables != 1)
     return fail(CBX_ERR_INVALID, "%s: use_variables %d is neither 0 nor 1", me, use_variables);
-  if (variables && p->var_bounds.empty()) return fail(CBX_ERR_STATE, "%s with variables before cbx_sma_plan_set_variables", me);
+  if (variables && p->var_bounds.empty())
+    return fail(CBX_ERR_STATE, "%s%s before cbx_sma_plan_set_variables", me, adaptive ? "" : " with variables");
+  if (adaptive) {
+    if (p->devs.empty() || !p->devs[0].adaptive_tables.dev || !p->devs[0].rate_matrix.dev)
+      return fail(CBX_ERR_STATE, "%s before cbx_sma_plan_set_adaptive", me);
+    if (!(clip.trust >= 0.0f) || std::isinf(clip.trust))
+      return fail(CBX_ERR_INVALID, "%s: trust %g is negative, NaN or infinite", me, (double)clip.trust);
+    if (!(clip.epsilon >= 0.0f) || std::isinf(clip.epsilon))
+      return fail(CBX_ERR_INVALID, "%s: epsilon %g is negative, NaN or infinite", me, (double)clip.epsilon);
+    if (clip.mode != 0 && clip.mode != 1)
+      return fail(CBX_ERR_INVALID, "%s: mode %d is neither 0 (LARS) nor 1 (LARC)", me, clip.mode);
+  }
   if (clipped && (!(clip.max_norm >= 0.0f) || std::isinf(clip.max_norm)))
     return fail(CBX_ERR_INVALID, "%s: max_norm %g is negative, NaN or infinite", me, (double)clip.max_norm);
   if (clipped && clip.skip_nonfinite != 0 && clip.skip_nonfinite != 1)
@@ -833,10 +851,16 @@ static int ea_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, floa
       return fail(CBX_ERR_INVALID, "%s: stepping replica %d: g must be non-null and 16-byte aligned", me, id);
     if (st && rmom && (!rlast[id] || !aligned16(rlast[id])))
       return fail(CBX_ERR_INVALID, "%s: stepping replica %d: replica momentum > 0 needs a 16-byte aligned last buffer", me, id);
-    if (clipped && st) TRY(take_clip_slot(me, id, clip.slot[id], &slots_taken));
+    if (adaptive && st) {
+      if (!clip.slot) return fail(CBX_ERR_INVALID, "%s: stepping replica %d without a slot list", me, id);
+      if (clip.slot[id] >= (int)p->devs[0].adaptive.size())
+        return fail(CBX_ERR_INVALID, "%s: stepping replica %d: slot %d out of range [0, %d)", me, id, clip.slot[id],
+                    (int)p->devs[0].adaptive.size());
+    }
+    if ((clipped || adaptive) && st) TRY(take_clip_slot(me, id, clip.slot[id], &slots_taken));
     if (++participating > cbx::kMaxReplicas) continue;  // counted on, refused below
     const int k = a.nrep++;
-    slot_of[k] = clipped && st ? clip.slot[id] : -1;
+    slot_of[k] = (clipped || adaptive) && st ? clip.slot[id] : -1;
     a.w[k] = reinterpret_cast<cbx::v4f *>(w[id]);
     if (st) {
       steps = true;
@@ -865,6 +889,25 @@ static int ea_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, floa
   cbx::ClipRecordPtrs records;
   const bool clips = clipped && steps;  // nobody steps: nothing to clip
   if (clips) TRY(plan_norm_passes(p, me, a, slot_of, clip, st0, records));
+  if (adaptive && steps) {
+    // The stepping replicas' norms in one batched pass and one trust launch
+    // over their slots' scratch, then the barrier, all three on streams[0].
+    cbx::ReplicaSteps rs;
+    for (int k = 0; k < a.nrep; ++k) {
+      if (slot_of[k] < 0) continue;
+      const int j = rs.count++;
+      rs.w[j] = reinterpret_cast<const float *>(a.w[k]);
+      rs.g[j] = reinterpret_cast<const float *>(a.g[k]);
+      rs.scratch[j] = &d.adaptive[(size_t)slot_of[k]];
+      rs.rate[j] = a.rate[k];
+      rs.col[j] = k;
+    }
+    const cbx::AdaptiveParams prm = {clip.trust, clip.epsilon, weight_decay, clip.mode};
+    HIP_TRY(cbx::launch_replica_norms(rs, d.adaptive_tables, d.var_tables.mult, prm, d.rate_matrix, d.var_tables.nvars,
+                                      p->adaptive_norm_policy, st0));
+    HIP_TRY(cbx::launch_task_elastic_adaptive(a, d.var_tables, d.rate_matrix, keep, cfg, st0, p->next_timing()));
+    return CBX_OK;
+  }
   HIP_TRY(cbx::pick_task_elastic_launch(a, variables ? &d.var_tables : nullptr, clips ? &records : nullptr, keep, cfg,
                                         st0, p->next_timing()));
   return CBX_OK;
@@ -892,6 +935,22 @@ int cbx_ea_plan_step_and_optimise_clipped_variables(cbx_sma_plan *p, void *const
   return ea_plan_step_and_optimise(p, streams, z, nreplicas, replica_device, w, s, g, rlast, locked, step,
                                    learning_rate, alpha, replica_momentum, weight_decay, first, flags, true, clip,
                                    use_variables);
+}
+
+int cbx_ea_plan_step_and_optimise_adaptive(cbx_sma_plan *p, void *const *streams, float *const *z, int nreplicas,
+                                           const int *replica_device, float *const *w, float *const *s,
+                                           float *const *g, float *const *rlast, const int *locked, const int *step,
+                                           const float *learning_rate, const int *slot, float trust, float epsilon,
+                                           int mode, float alpha, float replica_momentum, float weight_decay,
+                                           int first, unsigned flags) {
+  SeamClip ad;
+  ad.slot = slot;
+  ad.trust = trust;
+  ad.epsilon = epsilon;
+  ad.mode = mode;
+  return ea_plan_step_and_optimise(p, streams, z, nreplicas, replica_device, w, s, g, rlast, locked, step,
+                                   learning_rate, alpha, replica_momentum, weight_decay, first, flags, true, ad, 1,
+                                   true);
 }
 
 // crossbowSynchronisationSynchronousSGD (synch/synchronoussgd.c:13-106) over

@@ -1,7 +1,8 @@
-// task_elastic_body.inc -- the body of the four fused task-step
+// task_elastic_body.inc -- the body of the five fused task-step
 // elastic-averaging kernels (task_elastic_kernels.hip,
 // task_elastic_variables_kernels.hip, task_elastic_clipped_kernels.hip,
-// task_elastic_clipped_variables_kernels.hip), included inside each of them
+// task_elastic_clipped_variables_kernels.hip,
+// task_elastic_adaptive_kernels.hip), included inside each of them
 // behind its policy `step` (task_barrier_step.h).  The policy members are
 // those of task_barrier_body.inc, and the text is shared as text for that
 // file's reason.
@@ -18,7 +19,8 @@
 //     g = r * g ; g = fma(mu, last_i, g) ; last_i = g ; w' = fma(1, g, w)   :52-74
 //     or, without momentum, w' = fma(r, g, w)        :90
 //   with r = rate_i * mult[v] where the rate is per variable (model.c:159-177),
-//   else rate_i; with a clip record's skip bit the step is s = w and nothing
+//   r = (rate_i * mult[v]) * trust_i[v] out of the rate matrix where it is
+//   adaptive, else rate_i; with a clip record's skip bit the step is s = w and nothing
 //   else: last_i and g_i are stored with the bits that were loaded, w' = w_i.
 //   only joining: w' = w_i
 //   all: d = fma(-1, z, w') ; w_i = fma(-alpha, d, w') ; acc = fma(alpha, d, acc)   synchronouseamsgd.c:55-77
@@ -49,6 +51,7 @@
     // first float4 loads.
     [[maybe_unused]] uint32_t ch, e[U];
     [[maybe_unused]] v4f mv[U];
+    [[maybe_unused]] uint32_t vr[U][4];  // adaptive, a mixed chunk: the matrix row of each of the lane's four floats
     if constexpr (STEP::kPerVariable) {
       ch = (uint32_t)__builtin_amdgcn_readfirstlane((int)(base >> 6));
 #pragma unroll
@@ -97,7 +100,34 @@
       __builtin_amdgcn_sched_barrier(0);
       // byte offsets of the chunk's stores
       [[maybe_unused]] uint32_t so[U];
-      if constexpr (STEP::kPerVariable) {
+      [[maybe_unused]] float rt[U][RR];  // adaptive, a uniform chunk: the finished rates of this replica chunk
+      if constexpr (STEP::kAdaptive) {
+        // The finished rates (rate_k * m_v) * t_kv of this replica chunk
+        // (task_barrier_body.inc), behind the chunk's float4 loads.  A uniform
+        // chunk takes the RR consecutive floats of its variable's row from
+        // column c in one scalar load, once per replica chunk and not once per
+        // trip: the runtime-chunked form reads the next 8 columns each time
+        // round.  The column of a replica that only joins is loaded and not
+        // used.  In a chunk with a boundary inside each lane finds the row of
+        // each of its four floats once per trip and gathers the rates in the
+        // replica loop: RR x 4 of them per lane would not fit beside the streams.
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const uint32_t v0 = e[u] >> 1;
+          if ((e[u] & 1u) == 0u) {  // wave-uniform
+            uniform_rates<RR>(step.matrix + v0 * kMaxReplicas, c, rt[u]);
+          } else if (R > 0 || c == 0) {
+            const uint32_t f = (ch + u) * kOptChunk + lane * 4u;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) vr[u][k] = variable_of(step.bounds, step.nvars, v0, f + k) * kMaxReplicas;
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {  // the offsets, made opaque as below
+          so[u] = (base + u * 64u) * 16u;
+          asm volatile("" : "+v"(so[u]));
+        }
+      } else if constexpr (STEP::kPerVariable) {
         // The multipliers, once per trip and behind the first replica chunk's
         // loads.  In a chunk with a boundary inside, each lane finds the
         // variable of each of its four floats in the sorted boundary array.
@@ -143,7 +173,16 @@
           if (stepping) {
             // r_iv: a vector multiply of the (scalar) rate_i by the lane's four multipliers
             v4f rv = rate;
-            if constexpr (STEP::kPerVariable) rv = rate * mv[u];
+            if constexpr (STEP::kAdaptive) {  // finished: the barrier multiplies nothing
+              if ((e[u] & 1u) == 0u) {
+                rv = rt[u][r];
+              } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) rv[k] = step.matrix[vr[u][k] + (uint32_t)(c + r)];
+              }
+            } else if constexpr (STEP::kPerVariable) {
+              rv = rate * mv[u];
+            }
             v4f gv = y[u][r];
             if constexpr (STEP::kClips) gv = scale * y[u][r];
             if constexpr (WD) gv = vfma(wd, wv, gv);

@@ -1,10 +1,10 @@
-// task_elastic_launch.h -- what the four fused task-step elastic-averaging
+// task_elastic_launch.h -- what the five fused task-step elastic-averaging
 // kernels share beside their body (task_elastic_body.inc): the element-wise
 // tail, and the host side from the run-time arguments to one kernel
 // instantiation (launch_task_elastic, launch_task_elastic_variables,
-// launch_task_elastic_clipped, launch_task_elastic_clipped_variables).  The
-// policies are task_barrier_step.h's PlainStep, VariablesStep, ClippedStep and
-// ClippedVariablesStep.
+// launch_task_elastic_clipped, launch_task_elastic_clipped_variables,
+// launch_task_elastic_adaptive).  The policies are task_barrier_step.h's
+// PlainStep, VariablesStep, ClippedStep, ClippedVariablesStep and AdaptiveStep.
 //
 // Each compilation unit gives a launcher L:
 //   L::Step                         its step policy
@@ -32,10 +32,14 @@ template <bool MOM, bool WD, bool KEEP, class STEP>
 __device__ __forceinline__ void task_elastic_tail_elem(const TaskBarrierArgs &a, const STEP &step) {
   const int64_t i = a.tail_lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.tail_hi) return;
-  [[maybe_unused]] float m;  // the float's own multiplier
+  [[maybe_unused]] float m;      // the float's own multiplier
+  [[maybe_unused]] uint32_t vi;  // adaptive: the float's own row of the rate matrix
   if constexpr (STEP::kPerVariable) {
     const uint32_t en = step.chunks[(uint32_t)i / kOptChunk];
-    m = step.mult[(en & 1u) ? variable_of(step.bounds, step.nvars, en >> 1, (uint32_t)i) : (en >> 1)];
+    if constexpr (STEP::kAdaptive)
+      vi = ((en & 1u) ? variable_of(step.bounds, step.nvars, en >> 1, (uint32_t)i) : (en >> 1)) * kMaxReplicas;
+    else
+      m = step.mult[(en & 1u) ? variable_of(step.bounds, step.nvars, en >> 1, (uint32_t)i) : (en >> 1)];
   }
   float *z = reinterpret_cast<float *>(a.z);
   const float z0 = z[i];
@@ -66,7 +70,8 @@ __device__ __forceinline__ void task_elastic_tail_elem(const TaskBarrierArgs &a,
           [[maybe_unused]] bool skip = false;
           if constexpr (STEP::kClips) skip = (sf[r][1] & kClipSkipped) != 0u;
           float rate = a.rate[c + r];
-          if constexpr (STEP::kPerVariable) rate = a.rate[c + r] * m;  // model.c:159-177
+          if constexpr (STEP::kAdaptive) rate = step.matrix[vi + (uint32_t)(c + r)];  // (rate_k * m_v) * t_kv
+          else if constexpr (STEP::kPerVariable) rate = a.rate[c + r] * m;              // model.c:159-177
           float gv = y[r];
           if constexpr (STEP::kClips) gv = __uint_as_float(sf[r][0]) * y[r];
           if constexpr (WD) gv = fmaf(a.wd, x[r], gv);  // sma.cu:24-31
@@ -128,7 +133,7 @@ hipError_t te_u(const L &l, const TaskBarrierArgs &a, const LaunchConfig &cfg0, 
   // a clipped step keeps g always); one that only joins reads w and writes w.
   // For a policy that does not clip kKeepsG is MOM || WD, the condition of the
   // body's store of g: the counts, and with them the launch parameters, are
-  // one formula for all four policies.
+  // one formula for all five policies.
   int steps = 0;
   for (int r = 0; r < a.nrep; ++r) steps += (int)((a.step_mask >> r) & 1ull);
   const int joins = a.nrep - steps;

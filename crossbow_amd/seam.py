@@ -280,6 +280,27 @@ class SmaPlan:
             ctypes.c_float(weight_decay), first, ctypes.c_uint(flags)),
             "cbx_ea_plan_step_and_optimise_clipped_variables")
 
+    def elastic_step_and_optimise_adaptive(self, streams: Sequence[int], z: Sequence[int], replicas, alpha: float,
+                                           replica_momentum: float, weight_decay: float, first: int = 0,
+                                           flags: int = 0, slots: Optional[Sequence[int]] = None, trust: float = 0.0,
+                                           epsilon: float = 0.0, mode: int = 0) -> None:
+        """``elastic_step_and_optimise`` with the layer-wise adaptive step of
+        ``optimise_adaptive`` (``cbx_ea_plan_step_and_optimise_adaptive``; after
+        ``set_variables`` and ``set_adaptive``): the stepping replicas' norms
+        run as two batched launches on ``streams[0]`` over the scratch of
+        ``slots[id]``, then variable v of stepping replica id steps at
+        ``(learning_rate * multipliers[v]) * trust ratio`` inside the barrier's
+        launch.  Two stepping replicas take two slots; ``adaptive_stats`` reads
+        a slot's records afterwards.  Otherwise the same arguments."""
+        rate = (ctypes.c_float * max(1, len(replicas)))(*[float(r[7]) for r in replicas])
+        _raise(self.lib, self.lib.cbx_ea_plan_step_and_optimise_adaptive(
+            self._p, _ptrs(streams), _ptrs(z), len(replicas), _ints([r[0] for r in replicas]),
+            _ptrs([r[1] for r in replicas]), _ptrs([r[2] for r in replicas]), _ptrs([r[3] for r in replicas]),
+            _ptrs([r[4] for r in replicas]), _ints([r[5] for r in replicas]), _ints([r[6] for r in replicas]), rate,
+            _ints(slots) if slots is not None else None, ctypes.c_float(trust), ctypes.c_float(epsilon), mode,
+            ctypes.c_float(alpha), ctypes.c_float(replica_momentum), ctypes.c_float(weight_decay), first,
+            ctypes.c_uint(flags)), "cbx_ea_plan_step_and_optimise_adaptive")
+
     def polyak_step(self, streams: Sequence[int], z: Sequence[int], last: Optional[Sequence[Optional[int]]],
                     replicas: Sequence[Tuple[int, int, int, int]], alpha: float, clock: int, first: int = 0) -> int:
         """One Polyak-Ruppert barrier (``cbx_pr_plan_step``).  ``replicas[id]`` =

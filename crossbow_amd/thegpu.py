@@ -305,6 +305,20 @@ class TheGPU:
         return self._step_and_synchronise(self._L.cbx_step_and_synchronise_elastic_clipped_variables, first, clock,
                                           autotune, tasks, streams, flags)
 
+    def step_and_synchronise_elastic_adaptive(self, first: int, clock: int, autotune: int, tasks: Sequence[int],
+                                              streams: Optional[Sequence[Optional[int]]] = None,
+                                              flags: int = 0) -> int:
+        """``cbx_step_and_synchronise_elastic_adaptive``:
+        ``step_and_synchronise_elastic`` with layer-wise adaptive rates on
+        (``set_adaptive_rate``), which the other elastic fused calls refuse:
+        the stepping replicas' norms run as two batched launches on the sync
+        stream, and the step with each variable's trust ratio inside the
+        barrier's launch.  ``replica_adaptive_stats`` reads the records
+        afterwards.  Same arguments; with the rates off it is one of those
+        calls."""
+        return self._step_and_synchronise(self._L.cbx_step_and_synchronise_elastic_adaptive, first, clock, autotune,
+                                          tasks, streams, flags)
+
     def step_and_synchronise_ssgd(self, first: int, clock: int, autotune: int, tasks: Sequence[int],
                                   streams: Optional[Sequence[Optional[int]]] = None, flags: int = 0) -> int:
         """``cbx_step_and_synchronise_ssgd``: ``step_and_synchronise`` for

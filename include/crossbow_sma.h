@@ -501,6 +501,47 @@ int cbx_step_and_synchronise_elastic (cbx_context *ctx, int first, int clock, in
  * CBX_ERR_STATE for a stepping replica without clip scratch.                 */
 int cbx_step_and_synchronise_elastic_clipped_variables (cbx_context *ctx, int first, int clock, int autotune,
                                                         const int *tasks, void *const *streams, unsigned flags);
+/* cbx_step_and_synchronise_elastic with layer-wise adaptive rates on
+ * (cbx_set_adaptive_rate: LARS, or LARC as its capped form), which the two
+ * calls above refuse: what cbx_step_and_synchronise_adaptive is to the SMA
+ * barrier, for update model 3 with cbx_set_elastic_average on.  Same
+ * parameters, the same checks in the same order.  Asynchronous.
+ *
+ * Three launches on the sync stream, behind the callers' deferred waits: every
+ * stepping replica's two-buffer norm pass in one launch, one wave per
+ * (variable, stepping replica) that writes the replica's records
+ * (cbx_replica_adaptive_stats), its dense trust table and the finished rate
+ *   r_iv = (-learning_rate_i * mult[v]) * trust_i[v]
+ * into a variable-major matrix, and the barrier kernel
+ * (libcrossbow_sma_elastic_adaptive.so), which is
+ * cbx_step_and_synchronise_elastic_clipped_variables's per-variable arithmetic
+ * with r_iv read from the matrix in place of the product: it multiplies
+ * nothing.  mult[v] is 1 unless cbx_set_variable_learning_rates is on.
+ *
+ * The contract.  With flags == 0, z, every replica's w, s, g and `last`, every
+ * stepping replica's adaptive records and trust table and every piece of host
+ * state are left bit for bit as after
+ *   cbx_replica_optimise (ctx, id, tasks[id], streams[id])
+ *                                     for every id with tasks[id] >= 0, in id order,
+ *   cbx_synchronise (ctx, first, clock, autotune, 0)
+ * under elastic averaging.  With CBX_STEP_DISCARD_TASK_OUTPUTS, s_i and g_i of
+ * the stepping replicas are not written.  It moves (36R + 8) n bytes, (28R + 8) n
+ * with the discard flag, where the sequence moves (44R + 8) n, in 3 launches
+ * where the sequence takes 3R + 1.
+ *
+ * With the rates off the call launches what cbx_step_and_synchronise_elastic or
+ * cbx_step_and_synchronise_elastic_clipped_variables launches; when nobody
+ * steps it is the plain elastic barrier: no norm launch, no record touched.
+ *
+ * Everything is checked before the first side effect.  CBX_ERR_UNSUPPORTED:
+ * gradient clipping on as well; elastic averaging off or another update model
+ * (the SMA barrier takes cbx_step_and_synchronise_adaptive); a model without
+ * variable ranges or padded tables; more than one device or
+ * cbx_set_force_split; Nesterov's momentum; stepping replicas that differ in
+ * momentum or weight decay.  CBX_ERR_STATE: a stepping replica without
+ * adaptive scratch.  CBX_ERR_INVALID: as cbx_step_and_synchronise_elastic.  */
+int cbx_step_and_synchronise_elastic_adaptive (cbx_context *ctx, int first, int clock, int autotune,
+                                               const int *tasks, void *const *streams, unsigned flags);
 /* The pending task steps of the locked replicas and the one-GPU
  * synchronous-SGD barrier in one launch: cbx_step_and_synchronise for update
  * model WORKER (1; kernels/optimisers/synchronoussgd.cu:3-56 and
@@ -1817,6 +1858,37 @@ int cbx_ea_plan_step_and_optimise_clipped_variables (cbx_sma_plan *plan, void *c
                                    float *const *w, float *const *s, float *const *g, float *const *rlast,
                                    const int *locked, const int *step, const float *learning_rate,
                                    const int *slot, float max_norm, int skip_nonfinite, int use_variables,
+                                   float alpha, float replica_momentum, float weight_decay,
+                                   int first, unsigned flags);
+/* cbx_ea_plan_step_and_optimise with the layer-wise adaptive step of
+ * cbx_sma_plan_optimise_adaptive: what cbx_sma_plan_step_and_optimise_adaptive
+ * is to the SMA barrier, and cbx_step_and_synchronise_elastic_adaptive to a
+ * context.  After cbx_sma_plan_set_variables and cbx_sma_plan_set_adaptive.
+ * The arguments of cbx_ea_plan_step_and_optimise mean the same; slot, trust,
+ * epsilon and mode are cbx_sma_plan_step_and_optimise_adaptive's, under its
+ * slot rules: every stepping replica names a slot of its own among the plan's
+ * adaptive slots, whose records cbx_sma_plan_adaptive_stats reads afterwards.
+ * The stepping replicas' norms run as two batched launches on streams[0], then
+ * the barrier's launch; when nobody steps there is no norm launch, no record
+ * is touched and the launch is the per-variable one.
+ * The contract.  With flags == 0 every buffer (z, every w, rlast, s and g) and
+ * every stepping replica's slot (records and trust table) is left bit for bit
+ * as after cbx_sma_plan_optimise_adaptive for every id with step[id] != 0 in id
+ * order and then cbx_ea_plan_step.  With the discard flag, s[id] and g[id] of
+ * the stepping replicas are not written.  Nothing at or past `elements` is read
+ * or written.  One-device, one-rank plans only.
+ * Everything is checked before the first launch.  CBX_ERR_STATE: no variable
+ * table or no adaptive tables.  CBX_ERR_INVALID: as
+ * cbx_ea_plan_step_and_optimise; a trust or epsilon that is negative, NaN or
+ * infinite; a mode that is neither 0 (LARS) nor 1 (LARC); a stepping replica
+ * without a slot list, or its slot out of range or named twice.
+ * CBX_ERR_UNSUPPORTED: as cbx_ea_plan_step_and_optimise.
+ * Returns CBX_OK or an error.                                              */
+int cbx_ea_plan_step_and_optimise_adaptive (cbx_sma_plan *plan, void *const *streams, float *const *z,
+                                   int nreplicas, const int *replica_device,
+                                   float *const *w, float *const *s, float *const *g, float *const *rlast,
+                                   const int *locked, const int *step, const float *learning_rate,
+                                   const int *slot, float trust, float epsilon, int mode,
                                    float alpha, float replica_momentum, float weight_decay,
                                    int first, unsigned flags);
 /* crossbowSynchronisationPolyakRuppert (synch/polyakruppert.c:319 -> :5-138
