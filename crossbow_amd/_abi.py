@@ -134,6 +134,8 @@ SIGNATURES = {
     "cbx_step_and_synchronise_elastic_adaptive": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
     "cbx_step_and_synchronise_ssgd": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
     "cbx_step_and_synchronise_ssgd_clipped": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
+    "cbx_step_and_synchronise_ssgd_adaptive": (_I, [_P, _I, _I, _I, _IP, _PP, _c.c_uint]),
+    "cbx_base_adaptive_stats": (_I, [_P, _I, _AS, _I]),
     "cbx_replica_accumulate_clipped": (_I, [_P, _I, _I, _P]),
     "cbx_unlock_any": (_I, [_P]),
     "cbx_checkpoint_model": (_I, [_P, _CP]),
@@ -249,6 +251,8 @@ SIGNATURES = {
     "cbx_ssgd_plan_accumulate_clipped": (_I, [_P, _I, _I, _P, _P, _P, _P, _F, _F, _F, _I]),
     "cbx_ssgd_plan_step_and_optimise_clipped": (_I, [_P, _PP, _PP, _PP, _PP, _I, _IP, _PP, _PP, _IP, _IP, _FP, _IP,
                                                      _F, _I, _F, _F, _I, _I, _c.c_uint]),
+    "cbx_ssgd_plan_step_and_optimise_adaptive": (_I, [_P, _PP, _PP, _PP, _PP, _I, _IP, _PP, _PP, _IP, _IP, _FP, _I,
+                                                      _F, _F, _I, _F, _F, _I, _I, _c.c_uint]),
     "cbx_ea_plan_step": (_I, [_P, _PP, _PP, _I, _IP, _PP, _PP, _IP, _F, _I]),
     "cbx_ea_plan_step_and_optimise": (_I, [_P, _PP, _PP, _I, _IP, _PP, _PP, _PP, _PP, _IP, _IP, _FP, _F, _F, _F, _I,
                                            _c.c_uint]),

@@ -36,6 +36,10 @@
 * ``crossbow_amd/libcrossbow_sma_elastic_adaptive.so`` -- the task steps with
   layer-wise adaptive rates fused into the elastic-averaging barrier
   (csrc/task_elastic_adaptive_kernels.hip): likewise.
+* ``crossbow_amd/libcrossbow_sma_ssgd_adaptive.so`` -- the task steps with
+  layer-wise adaptive rates fused into the synchronous-SGD barrier: the
+  accumulate-and-norm pass, the trust kernel and the apply-and-broadcast kernel
+  (csrc/task_ssgd_adaptive_kernels.hip): likewise.
 * ``crossbow_amd/libGPU.so``           -- the JNI shim exporting Crossbow's
   ``TheGPU`` model-path natives; built only where ``jni.h`` exists (there is
   no JDK in this image).
@@ -64,6 +68,7 @@ SSGD_CLIPPED_LIB = os.path.join(PKG, "libcrossbow_sma_ssgd_clipped.so")
 ADAPTIVE_LIB = os.path.join(PKG, "libcrossbow_sma_adaptive.so")
 ADAPTIVE_STEPS_LIB = os.path.join(PKG, "libcrossbow_sma_adaptive_steps.so")
 ELASTIC_ADAPTIVE_LIB = os.path.join(PKG, "libcrossbow_sma_elastic_adaptive.so")
+SSGD_ADAPTIVE_LIB = os.path.join(PKG, "libcrossbow_sma_ssgd_adaptive.so")
 JNI_LIB = os.path.join(PKG, "libGPU.so")
 ARCH = "gfx950"
 
@@ -88,9 +93,11 @@ SSGD_CLIPPED_SOURCES = ("task_ssgd_clipped_kernels.hip",)
 ADAPTIVE_SOURCES = ("adaptive_rate_kernels.hip",)
 ADAPTIVE_STEPS_SOURCES = ("task_barrier_adaptive_kernels.hip",)
 ELASTIC_ADAPTIVE_SOURCES = ("task_elastic_adaptive_kernels.hip",)
+SSGD_ADAPTIVE_SOURCES = ("task_ssgd_adaptive_kernels.hip",)
 HEADERS = ("context_internal.h", "sma_internal.h", "stream_helpers.h", "stats_internal.h", "stats_plan.h",
            "optimise_plan.h", "clip_internal.h", "bucket_pipeline.h", "task_ssgd_internal.h",
            "task_ssgd_clipped_internal.h", "adaptive_internal.h", "adaptive_steps_internal.h",
+           "task_ssgd_adaptive_internal.h",
            # the fused task-step barrier's five kernel files are one text
            "task_barrier_step.h", "task_barrier_body.inc", "task_barrier_launch.h",
            # and so are the five of the fused elastic-averaging barrier
@@ -105,7 +112,7 @@ def _deps():
     return (_sources() + _sources(VARIABLES_SOURCES) + _sources(CLIPPED_SOURCES) +
             _sources(CLIPPED_VARIABLES_SOURCES) + _sources(ELASTIC_STEPS_SOURCES) + _sources(SSGD_STEPS_SOURCES) +
             _sources(ELASTIC_POLICIES_SOURCES) + _sources(SSGD_CLIPPED_SOURCES) + _sources(ADAPTIVE_SOURCES) +
-            _sources(ADAPTIVE_STEPS_SOURCES) + _sources(ELASTIC_ADAPTIVE_SOURCES) +
+            _sources(ADAPTIVE_STEPS_SOURCES) + _sources(ELASTIC_ADAPTIVE_SOURCES) + _sources(SSGD_ADAPTIVE_SOURCES) +
             [os.path.join(CSRC, f) for f in HEADERS] + [os.path.join(ROOT, "include", "crossbow_sma.h"),
                                                         os.path.abspath(__file__)])
 
@@ -162,39 +169,41 @@ def _link(target, objs, libs, verbose):
 
 
 def build_lib(force: bool = False, verbose: bool = False) -> str:
-    # one staleness check for all eleven libraries: they share the headers
+    # one staleness check for all twelve libraries: they share the headers
     if not force and not any(_stale(t, _deps()) for t in (LIB, VARIABLES_LIB, CLIPPED_LIB, CLIPPED_VARIABLES_LIB,
                                                           ELASTIC_STEPS_LIB, SSGD_STEPS_LIB, ELASTIC_POLICIES_LIB,
                                                           SSGD_CLIPPED_LIB, ADAPTIVE_LIB, ADAPTIVE_STEPS_LIB,
-                                                          ELASTIC_ADAPTIVE_LIB)):
+                                                          ELASTIC_ADAPTIVE_LIB, SSGD_ADAPTIVE_LIB)):
         return LIB
     objdir = os.path.join(PKG, "build")
     os.makedirs(objdir, exist_ok=True)
-    # every source of the eleven objects is compiled in one pool, the slowest (the barrier kernels) first
-    groups = (ELASTIC_ADAPTIVE_SOURCES, ADAPTIVE_STEPS_SOURCES, VARIABLES_SOURCES, CLIPPED_SOURCES, CLIPPED_VARIABLES_SOURCES, ELASTIC_STEPS_SOURCES, SSGD_STEPS_SOURCES,
+    # every source of the twelve objects is compiled in one pool, the slowest (the barrier kernels) first
+    groups = (SSGD_ADAPTIVE_SOURCES, ELASTIC_ADAPTIVE_SOURCES, ADAPTIVE_STEPS_SOURCES, VARIABLES_SOURCES, CLIPPED_SOURCES, CLIPPED_VARIABLES_SOURCES, ELASTIC_STEPS_SOURCES, SSGD_STEPS_SOURCES,
               ELASTIC_POLICIES_SOURCES, SSGD_CLIPPED_SOURCES, ADAPTIVE_SOURCES, tuple(reversed(SOURCES)))
     objs = _compile([src for names in groups for src in _sources(names)], objdir, verbose)
-    side = (len(ELASTIC_ADAPTIVE_SOURCES), len(ADAPTIVE_STEPS_SOURCES), len(VARIABLES_SOURCES), len(CLIPPED_SOURCES), len(CLIPPED_VARIABLES_SOURCES), len(ELASTIC_STEPS_SOURCES),
+    side = (len(SSGD_ADAPTIVE_SOURCES), len(ELASTIC_ADAPTIVE_SOURCES), len(ADAPTIVE_STEPS_SOURCES), len(VARIABLES_SOURCES), len(CLIPPED_SOURCES), len(CLIPPED_VARIABLES_SOURCES), len(ELASTIC_STEPS_SOURCES),
             len(SSGD_STEPS_SOURCES), len(ELASTIC_POLICIES_SOURCES), len(SSGD_CLIPPED_SOURCES), len(ADAPTIVE_SOURCES))
-    at = [sum(side[:k]) for k in range(11)]
+    at = [sum(side[:k]) for k in range(12)]
     # the objects of the per-variable, the clipped and the clipped per-variable fused barrier, of the fused
     # elastic-averaging and synchronous-SGD barriers, of the former's policies, of the latter's clipped form and of
-    # the adaptive step and of the adaptive fused SMA and elastic barriers first: the library links against them
-    _link(ELASTIC_ADAPTIVE_LIB, objs[at[0]:at[1]], [], verbose)
-    _link(ADAPTIVE_STEPS_LIB, objs[at[1]:at[2]], [], verbose)
-    _link(VARIABLES_LIB, objs[at[2]:at[3]], [], verbose)
-    _link(CLIPPED_LIB, objs[at[3]:at[4]], [], verbose)
-    _link(CLIPPED_VARIABLES_LIB, objs[at[4]:at[5]], [], verbose)
-    _link(ELASTIC_STEPS_LIB, objs[at[5]:at[6]], [], verbose)
-    _link(SSGD_STEPS_LIB, objs[at[6]:at[7]], [], verbose)
-    _link(ELASTIC_POLICIES_LIB, objs[at[7]:at[8]], [], verbose)
-    _link(SSGD_CLIPPED_LIB, objs[at[8]:at[9]], [], verbose)
-    _link(ADAPTIVE_LIB, objs[at[9]:at[10]], [], verbose)
-    _link(LIB, list(reversed(objs[at[10]:])),
+    # the adaptive step and of the adaptive fused SMA, elastic and synchronous-SGD barriers first: the library links
+    # against them
+    _link(SSGD_ADAPTIVE_LIB, objs[at[0]:at[1]], [], verbose)
+    _link(ELASTIC_ADAPTIVE_LIB, objs[at[1]:at[2]], [], verbose)
+    _link(ADAPTIVE_STEPS_LIB, objs[at[2]:at[3]], [], verbose)
+    _link(VARIABLES_LIB, objs[at[3]:at[4]], [], verbose)
+    _link(CLIPPED_LIB, objs[at[4]:at[5]], [], verbose)
+    _link(CLIPPED_VARIABLES_LIB, objs[at[5]:at[6]], [], verbose)
+    _link(ELASTIC_STEPS_LIB, objs[at[6]:at[7]], [], verbose)
+    _link(SSGD_STEPS_LIB, objs[at[7]:at[8]], [], verbose)
+    _link(ELASTIC_POLICIES_LIB, objs[at[8]:at[9]], [], verbose)
+    _link(SSGD_CLIPPED_LIB, objs[at[9]:at[10]], [], verbose)
+    _link(ADAPTIVE_LIB, objs[at[10]:at[11]], [], verbose)
+    _link(LIB, list(reversed(objs[at[11]:])),
           ["-L", PKG, "-lcrossbow_sma_variables", "-lcrossbow_sma_clipped", "-lcrossbow_sma_clipped_variables",
            "-lcrossbow_sma_elastic_steps", "-lcrossbow_sma_ssgd_steps", "-lcrossbow_sma_elastic_policies",
            "-lcrossbow_sma_ssgd_clipped", "-lcrossbow_sma_adaptive", "-lcrossbow_sma_adaptive_steps",
-           "-lcrossbow_sma_elastic_adaptive",
+           "-lcrossbow_sma_elastic_adaptive", "-lcrossbow_sma_ssgd_adaptive",
            "-Wl,-rpath,$ORIGIN", "-lrccl", "-lrocprofiler-sdk-roctx", "-lpthread"],
           verbose)
     return LIB

@@ -16,6 +16,7 @@
 //   * errors return codes; the JNI shim turns them back into exit(1).
 #include "context_internal.h"
 #include "optimise_plan.h"
+#include "task_ssgd_adaptive_internal.h"
 #include "task_ssgd_clipped_internal.h"
 #include "task_ssgd_internal.h"
 
@@ -508,6 +509,8 @@ static int build_variable_tables(cbx_context *c) {
     HIP_TRY(cbx::adaptive_tables_upload(d.adaptive_tables, pieces, adaptive.data()));
     HIP_TRY(cbx::rate_matrix_alloc(d.rate_matrix, d.adaptive_tables));
     for (int id : d.replicas) HIP_TRY(cbx::adaptive_scratch_alloc(c->replicas[id]->adaptive, d.adaptive_tables));
+    // and the base model its own, for the adaptive synchronous-SGD barrier
+    HIP_TRY(cbx::adaptive_scratch_alloc(d.base_adaptive, d.adaptive_tables));
   }
   c->var_bounds = plan.bounds;
   return CBX_OK;
@@ -763,7 +766,8 @@ static int check_fused_call(cbx_context *c, const char *me, int first, const int
     return fail(CBX_ERR_UNSUPPORTED, "%s: layer-wise adaptive rates are on (cbx_set_adaptive_rate); the adaptive step "
                 "needs its norm pass first and is fused into the one-GPU SMA and elastic-averaging barriers only, use "
                 "cbx_step_and_synchronise_adaptive or cbx_step_and_synchronise_elastic_adaptive, or "
-                "cbx_replica_optimise and cbx_synchronise", me);
+                "cbx_replica_optimise and cbx_synchronise; update model WORKER takes "
+                "cbx_step_and_synchronise_ssgd_adaptive", me);
   const int size = c->size;
   for (int id = 0; id < size; ++id) {
     if (tasks[id] < -1) return fail(CBX_ERR_INVALID, "%s: tasks[%d] = %d is neither a task number nor -1", me, id, tasks[id]);
@@ -1216,23 +1220,50 @@ int cbx_step_and_synchronise_elastic_adaptive(cbx_context *c, int first, int clo
 // (launch_fused_norms) and the kernel with the clipped step
 // (task_ssgd_clipped_kernels.hip); with clipping off, or nobody stepping, it is
 // the plain call's launch.
+// cbx_step_and_synchronise_ssgd_adaptive (SsgdAdaptive) is the one
+// synchronous-SGD call that passes with layer-wise adaptive rates on: behind the
+// callers' deferred waits it enqueues the accumulate-and-norm pass, the trust
+// kernel and the apply-and-broadcast kernel on the sync stream
+// (task_ssgd_adaptive_kernels.hip), the records in the device's base scratch
+// (cbx_base_adaptive_stats).  It refuses clipping; with the rates off, or
+// nobody stepping, it is the plain call's launch and touches no record.
+enum SsgdMode { SsgdPlain, SsgdClipped, SsgdAdaptive };
+
 static int step_and_synchronise_ssgd(cbx_context *c, int first, int clock, int autotune, const int *tasks,
-                                     void *const *streams, unsigned flags, bool clipped) {
-  const char *me = clipped ? "cbx_step_and_synchronise_ssgd_clipped" : "cbx_step_and_synchronise_ssgd";
-  const char *instead = clipped ? "cbx_replica_accumulate_clipped and cbx_synchronise"
-                                : "cbx_replica_optimise and cbx_synchronise";
+                                     void *const *streams, unsigned flags, SsgdMode mode) {
+  const bool clipped = mode == SsgdClipped;
+  const char *me = mode == SsgdAdaptive ? "cbx_step_and_synchronise_ssgd_adaptive"
+                   : clipped            ? "cbx_step_and_synchronise_ssgd_clipped"
+                                        : "cbx_step_and_synchronise_ssgd";
+  const bool adaptive = c && c->adaptive_on();  // only SsgdAdaptive comes past check_fused_call with them on
+  // with the rates on there is no two-call sequence to name: the task step refuses them
+  const char *instead = adaptive  ? "cbx_replica_optimise and cbx_synchronise with the rates off (cbx_set_adaptive_rate)"
+                        : clipped ? "cbx_replica_accumulate_clipped and cbx_synchronise"
+                                  : "cbx_replica_optimise and cbx_synchronise";
   TraceRange trace(me);
-  TRY(check_fused_call(c, me, first, tasks, flags, instead));
+  TRY(check_fused_call(c, me, first, tasks, flags, instead, mode == SsgdAdaptive));
   const int size = c->size;
   const int type = c->model.type;
   if (type != CBX_UPDATE_WORKER)
-    return fail(CBX_ERR_UNSUPPORTED, "%s: update model %d; only WORKER (1) is fused here; %s", me, type,
+    return fail(CBX_ERR_UNSUPPORTED, "%s: update model %d; only WORKER (1) is fused here; %s%s", me, type,
                 type == CBX_UPDATE_SYNCHRONOUSEAMSGD && c->elastic_average
                     ? "elastic averaging takes cbx_step_and_synchronise_elastic"
                 : type == CBX_UPDATE_SMA || type == CBX_UPDATE_SYNCHRONOUSEAMSGD
                     ? "the SMA barrier takes cbx_step_and_synchronise"
-                    : "use cbx_replica_optimise and cbx_synchronise");
+                    : "use cbx_replica_optimise and cbx_synchronise",
+                !adaptive                                                          ? ""
+                : type == CBX_UPDATE_SMA || type == CBX_UPDATE_SYNCHRONOUSEAMSGD ? "_adaptive"
+                                                                                   : " with the rates off (cbx_set_adaptive_rate)");
   const bool clip = c->clip_on();
+  if (adaptive && clip)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: layer-wise adaptive rates and gradient clipping are both on: the two are not "
+                "composed yet; turn one off (cbx_set_gradient_clip or cbx_set_adaptive_rate)", me);
+  if (adaptive && !c->var_refusal.empty())
+    return fail(CBX_ERR_UNSUPPORTED, "%s with layer-wise adaptive rates (cbx_set_adaptive_rate): %s; turn them off for "
+                "cbx_step_and_synchronise_ssgd", me, c->var_refusal.c_str());
+  if (adaptive && !c->devs[0].var_tables_padded.chunks)
+    return fail(CBX_ERR_UNSUPPORTED, "%s: the padded model is too large for the chunk table; turn the rates off "
+                "(cbx_set_adaptive_rate) for cbx_step_and_synchronise_ssgd", me);
   if (clip && !clipped)
     return fail(CBX_ERR_UNSUPPORTED, "%s: gradient clipping is on, and update model WORKER has no clipped step; turn it "
                 "off (cbx_set_gradient_clip) and use %s", me, instead);
@@ -1261,6 +1292,10 @@ static int step_and_synchronise_ssgd(cbx_context *c, int first, int clock, int a
   for (int id = 0; clip && id < size; ++id)
     if (tasks[id] >= 0 && !c->replicas[id]->clip.dev)
       return fail(CBX_ERR_STATE, "replica %d has no gradient-clip scratch", id);
+  const bool adaptive_steps = adaptive && ref != nullptr;  // nobody steps: the plain barrier, no norm launch
+  if (adaptive_steps && (!d.adaptive_tables.dev || !d.base_adaptive.dev ||
+                         d.adaptive_tables.nvars + 1 != d.var_tables_padded.nvars))
+    return fail(CBX_ERR_STATE, "%s: device %d has no adaptive-rate tables", me, d.g);
 
   std::vector<float> lr((size_t)size, 0.0f);
   TRY(query_rates(c, tasks, lr));
@@ -1307,8 +1342,17 @@ static int step_and_synchronise_ssgd(cbx_context *c, int first, int clock, int a
   cfg.num_cus = d.num_cus;
   const bool keep = (flags & CBX_STEP_DISCARD_TASK_OUTPUTS) == 0;
   const cbx::Timing tm = {step_start_event(c, d, 0), step_stop_event(c, d, EV_A)};
-  if (norms.empty()) HIP_TRY(cbx::launch_task_ssgd(a, keep, cfg, d.stream, tm));
-  else HIP_TRY(cbx::launch_task_ssgd_clipped(a, records, keep, cfg, d.stream, tm));
+  if (adaptive_steps) {
+    // In order on the sync stream the three launches are behind the previous
+    // barrier's use of the base scratch.  beta is the stepping replicas' weight decay.
+    const cbx::AdaptiveParams prm = {c->adaptive_trust, c->adaptive_epsilon, a.wd, c->adaptive_mode};
+    HIP_TRY(cbx::launch_task_ssgd_adaptive(a, d.adaptive_tables, d.base_adaptive, prm, d.var_tables_padded, keep, cfg,
+                                           d.stream, tm));
+  } else if (norms.empty()) {
+    HIP_TRY(cbx::launch_task_ssgd(a, keep, cfg, d.stream, tm));
+  } else {
+    HIP_TRY(cbx::launch_task_ssgd_clipped(a, records, keep, cfg, d.stream, tm));
+  }
   close_fused_step(c, d);  // the ring slot, cross_valid = false, last_step_split = false: ssgd_step's unsplit form
   TRY(finish_step(c));
   return finish_barrier(c, clock, autotune);
@@ -1316,12 +1360,17 @@ static int step_and_synchronise_ssgd(cbx_context *c, int first, int clock, int a
 
 int cbx_step_and_synchronise_ssgd(cbx_context *c, int first, int clock, int autotune, const int *tasks,
                                   void *const *streams, unsigned flags) {
-  return step_and_synchronise_ssgd(c, first, clock, autotune, tasks, streams, flags, false);
+  return step_and_synchronise_ssgd(c, first, clock, autotune, tasks, streams, flags, SsgdPlain);
 }
 
 int cbx_step_and_synchronise_ssgd_clipped(cbx_context *c, int first, int clock, int autotune, const int *tasks,
                                           void *const *streams, unsigned flags) {
-  return step_and_synchronise_ssgd(c, first, clock, autotune, tasks, streams, flags, true);
+  return step_and_synchronise_ssgd(c, first, clock, autotune, tasks, streams, flags, SsgdClipped);
+}
+
+int cbx_step_and_synchronise_ssgd_adaptive(cbx_context *c, int first, int clock, int autotune, const int *tasks,
+                                           void *const *streams, unsigned flags) {
+  return step_and_synchronise_ssgd(c, first, clock, autotune, tasks, streams, flags, SsgdAdaptive);
 }
 
 int cbx_unlock_any(cbx_context *c) {
@@ -2010,8 +2059,9 @@ static int replica_optimise_impl(cbx_context *c, int id, int task, void *stream)
       return fail(CBX_ERR_UNSUPPORTED,
                   "cbx_replica_optimise with layer-wise adaptive rates on: update model %d (%s) steps the base model "
                   "on the sync stream and has no adaptive step; turn them off (cbx_set_adaptive_rate) for "
-                  "cbx_replica_optimise, they cover SMA and SYNCHRONOUSEAMSGD",
-                  type, type == CBX_UPDATE_WORKER ? "WORKER" : "DEFAULT");
+                  "cbx_replica_optimise, they cover SMA and SYNCHRONOUSEAMSGD%s",
+                  type, type == CBX_UPDATE_WORKER ? "WORKER" : "DEFAULT",
+                  type == CBX_UPDATE_WORKER ? ", and WORKER's fused barrier: cbx_step_and_synchronise_ssgd_adaptive" : "");
     if (c->clip_on())
       return fail(CBX_ERR_UNSUPPORTED,
                   "cbx_replica_optimise with layer-wise adaptive rates and gradient clipping both on: the two are not "
@@ -2512,6 +2562,24 @@ int cbx_replica_adaptive_stats(cbx_context *c, int id, cbx_adaptive_stats *out, 
   HIP_TRY(hipSetDevice(d.hip_id));
   HIP_TRY(hipStreamSynchronize(d.stream));
   if (count > 0) HIP_TRY(hipMemcpy(out, r.adaptive.records(), (size_t)count * sizeof(*out), hipMemcpyDeviceToHost));
+  return CBX_OK;
+}
+
+int cbx_base_adaptive_stats(cbx_context *c, int g, cbx_adaptive_stats *out, int count) {
+  TRY(check_manager(c));
+  if (!out) return fail(CBX_ERR_INVALID, "cbx_base_adaptive_stats: null result");
+  const int k = local_of(c, g);
+  if (k < 0) return fail(CBX_ERR_INVALID, "device %d is not driven by this process", g);
+  Device &d = c->devs[(size_t)k];
+  if (!d.base_adaptive.dev)
+    return fail(CBX_ERR_STATE, "device %d has no adaptive-rate scratch%s%s", g, c->var_refusal.empty() ? "" : ": ",
+                c->var_refusal.c_str());
+  if (count < 0 || count > (int)d.base_adaptive.nvars)
+    return fail(CBX_ERR_INVALID, "cbx_base_adaptive_stats: count %d out of range [0, %u]", count, d.base_adaptive.nvars);
+  TRY(flush_task_waits(c));
+  HIP_TRY(hipSetDevice(d.hip_id));
+  HIP_TRY(hipStreamSynchronize(d.stream));
+  if (count > 0) HIP_TRY(hipMemcpy(out, d.base_adaptive.records(), (size_t)count * sizeof(*out), hipMemcpyDeviceToHost));
   return CBX_OK;
 }
 

@@ -413,6 +413,9 @@ struct Device {
   cbx::AdaptiveTables adaptive_tables;
   // cbx_step_and_synchronise_adaptive: the finished rates of one call, nvars + 1 rows
   cbx::RateMatrix rate_matrix;
+  // cbx_step_and_synchronise_ssgd_adaptive: the base model's records, trust table and partials
+  // (cbx_base_adaptive_stats)
+  cbx::AdaptiveScratch base_adaptive;
   int num_cus = 256;
   // Arena: [base data][base gradient(ctrl+acc)][base diff(ctrl+D)][base last]
   //        then per replica [data][diff][last][gradient].
@@ -910,6 +913,7 @@ inline void close_device(Device &d) {
   cbx::var_tables_free(d.var_tables_padded);
   cbx::adaptive_tables_free(d.adaptive_tables);
   cbx::rate_matrix_free(d.rate_matrix);
+  cbx::adaptive_scratch_free(d.base_adaptive);
   if (d.host) (void)hipHostFree(d.host);
   if (d.synched) (void)hipEventDestroy(d.synched);
   for (int k = 0; k < EV_COUNT; ++k)

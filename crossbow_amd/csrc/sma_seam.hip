@@ -33,6 +33,7 @@
 // which they are enqueued, its diagrams, and the bucket geometry.
 #include "context_internal.h"
 #include "optimise_plan.h"
+#include "task_ssgd_adaptive_internal.h"
 #include "task_ssgd_clipped_internal.h"
 #include "task_ssgd_internal.h"
 
@@ -528,7 +529,10 @@ struct SeamClip {
   // SeamAdaptive: trust, epsilon and the mode of cbx_sma_plan_optimise_adaptive
   float trust = 0.0f, epsilon = 0.0f;
   int mode = 0;
+  int base_slot = 0;  // SsgdSeamAdaptive: the one adaptive slot of the base model's records
 };
+// The three doors of ssgd_plan_step_and_optimise.
+enum SsgdSeamMode { SsgdSeamPlain, SsgdSeamClipped, SsgdSeamAdaptive };
 }  // namespace
 
 // Stepping replica id's slot of a clipped call: in range, and no other stepping
@@ -1013,14 +1017,36 @@ int cbx_ssgd_plan_step(cbx_sma_plan *p, void *const *streams, float *const *z, f
 // id order, in front of the launch, and the clipped step inside it
 // (task_ssgd_clipped_kernels.hip): the slot rules are SeamClipped's.  When
 // nobody steps it is the plain call's launch.
+// cbx_ssgd_plan_step_and_optimise_adaptive (SsgdSeamAdaptive; clip.base_slot is
+// the base model's one adaptive slot): the accumulate-and-norm pass, the trust
+// kernel and the apply-and-broadcast kernel on streams[0]
+// (task_ssgd_adaptive_kernels.hip), over the plan's variable and piece tables.
+// When nobody steps it is the plain call's launch and the slot is not touched.
 static int ssgd_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float *const *z, float *const *last,
                                        float *const *acc, int nreplicas, const int *replica_device, float *const *w,
                                        float *const *g, const int *locked, const int *step,
                                        const float *learning_rate, float momentum, float weight_decay, int wpc,
-                                       int first, unsigned flags, bool clipped, const SeamClip &clip = SeamClip()) {
-  const char *me = clipped ? "cbx_ssgd_plan_step_and_optimise_clipped" : "cbx_ssgd_plan_step_and_optimise";
+                                       int first, unsigned flags, SsgdSeamMode door,
+                                       const SeamClip &clip = SeamClip()) {
+  const bool clipped = door == SsgdSeamClipped, adaptive = door == SsgdSeamAdaptive;
+  const char *me = adaptive  ? "cbx_ssgd_plan_step_and_optimise_adaptive"
+                   : clipped ? "cbx_ssgd_plan_step_and_optimise_clipped"
+                             : "cbx_ssgd_plan_step_and_optimise";
   TraceRange trace(me);
   if (!p) return fail(CBX_ERR_INVALID, "null plan");
+  if (adaptive) {
+    if (p->var_bounds.empty()) return fail(CBX_ERR_STATE, "%s before cbx_sma_plan_set_variables", me);
+    if (p->devs.empty() || !p->devs[0].adaptive_tables.dev)
+      return fail(CBX_ERR_STATE, "%s before cbx_sma_plan_set_adaptive", me);
+    if (clip.base_slot < 0 || clip.base_slot >= (int)p->devs[0].adaptive.size())
+      return fail(CBX_ERR_INVALID, "%s: slot %d out of range [0, %d)", me, clip.base_slot, (int)p->devs[0].adaptive.size());
+    if (!(clip.trust >= 0.0f) || std::isinf(clip.trust))
+      return fail(CBX_ERR_INVALID, "%s: trust %g is negative, NaN or infinite", me, (double)clip.trust);
+    if (!(clip.epsilon >= 0.0f) || std::isinf(clip.epsilon))
+      return fail(CBX_ERR_INVALID, "%s: epsilon %g is negative, NaN or infinite", me, (double)clip.epsilon);
+    if (clip.mode != 0 && clip.mode != 1)
+      return fail(CBX_ERR_INVALID, "%s: mode %d is neither 0 (LARS) nor 1 (LARC)", me, clip.mode);
+  }
   if (clipped && (!(clip.max_norm >= 0.0f) || std::isinf(clip.max_norm)))
     return fail(CBX_ERR_INVALID, "%s: max_norm %g is negative, NaN or infinite", me, (double)clip.max_norm);
   if (clipped && clip.skip_nonfinite != 0 && clip.skip_nonfinite != 1)
@@ -1088,6 +1114,12 @@ static int ssgd_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, fl
   cbx::LaunchConfig cfg = p->task_barrier_cfg;
   cfg.num_cus = d.num_cus;
   hipStream_t st0 = static_cast<hipStream_t>(streams[0]);
+  if (adaptive && a.nstep > 0) {
+    const cbx::AdaptiveParams prm = {clip.trust, clip.epsilon, a.wd, clip.mode};
+    HIP_TRY(cbx::launch_task_ssgd_adaptive(a, d.adaptive_tables, d.adaptive[(size_t)clip.base_slot], prm, d.var_tables,
+                                           keep, cfg, st0, p->next_timing()));
+    return CBX_OK;
+  }
   if (!clipped || a.nstep == 0) {  // nobody steps: nothing to clip
     HIP_TRY(cbx::launch_task_ssgd(a, keep, cfg, st0, p->next_timing()));
     return CBX_OK;
@@ -1113,7 +1145,7 @@ int cbx_ssgd_plan_step_and_optimise(cbx_sma_plan *p, void *const *streams, float
                                     float *const *g, const int *locked, const int *step, const float *learning_rate,
                                     float momentum, float weight_decay, int wpc, int first, unsigned flags) {
   return ssgd_plan_step_and_optimise(p, streams, z, last, acc, nreplicas, replica_device, w, g, locked, step,
-                                     learning_rate, momentum, weight_decay, wpc, first, flags, false);
+                                     learning_rate, momentum, weight_decay, wpc, first, flags, SsgdSeamPlain);
 }
 
 int cbx_ssgd_plan_step_and_optimise_clipped(cbx_sma_plan *p, void *const *streams, float *const *z,
@@ -1127,7 +1159,22 @@ int cbx_ssgd_plan_step_and_optimise_clipped(cbx_sma_plan *p, void *const *stream
   clip.max_norm = max_norm;
   clip.skip_nonfinite = skip_nonfinite;
   return ssgd_plan_step_and_optimise(p, streams, z, last, acc, nreplicas, replica_device, w, g, locked, step,
-                                     learning_rate, momentum, weight_decay, wpc, first, flags, true, clip);
+                                     learning_rate, momentum, weight_decay, wpc, first, flags, SsgdSeamClipped, clip);
+}
+
+int cbx_ssgd_plan_step_and_optimise_adaptive(cbx_sma_plan *p, void *const *streams, float *const *z,
+                                             float *const *last, float *const *acc, int nreplicas,
+                                             const int *replica_device, float *const *w, float *const *g,
+                                             const int *locked, const int *step, const float *learning_rate,
+                                             int slot, float trust, float epsilon, int mode, float momentum,
+                                             float weight_decay, int wpc, int first, unsigned flags) {
+  SeamClip ad;
+  ad.base_slot = slot;
+  ad.trust = trust;
+  ad.epsilon = epsilon;
+  ad.mode = mode;
+  return ssgd_plan_step_and_optimise(p, streams, z, last, acc, nreplicas, replica_device, w, g, locked, step,
+                                     learning_rate, momentum, weight_decay, wpc, first, flags, SsgdSeamAdaptive, ad);
 }
 
 // crossbowKernelOptimiserSynchronousSGD (kernels/optimisers/synchronoussgd.cu:

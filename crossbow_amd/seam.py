@@ -223,6 +223,29 @@ class SmaPlan:
             ctypes.c_float(momentum), ctypes.c_float(weight_decay), wpc, first, ctypes.c_uint(flags)),
             "cbx_ssgd_plan_step_and_optimise_clipped")
 
+    def ssgd_step_and_optimise_adaptive(self, streams: Sequence[int], z: Sequence[int],
+                                        last: Optional[Sequence[Optional[int]]], acc: Sequence[int],
+                                        replicas: Sequence[Tuple[int, int, Optional[int], int, int, float]],
+                                        momentum: float, weight_decay: float, wpc: int, first: int = 0, flags: int = 0,
+                                        slot: int = 0, trust: float = 0.0, epsilon: float = 0.0,
+                                        mode: int = 0) -> None:
+        """``ssgd_step_and_optimise`` with layer-wise adaptive rates
+        (``cbx_ssgd_plan_step_and_optimise_adaptive``; after ``set_variables``
+        and ``set_adaptive``): the accumulated update of variable v is scaled
+        by the trust ratio of the base model's norm and the norm of the mean of
+        the stepping replicas' raw gradients.  Three launches on
+        ``streams[0]``; ``slot`` takes the base model's records, which
+        ``adaptive_stats(0, slot, ...)`` reads afterwards.  Otherwise the same
+        arguments."""
+        rate = (ctypes.c_float * max(1, len(replicas)))(*[float(r[5]) for r in replicas])
+        _raise(self.lib, self.lib.cbx_ssgd_plan_step_and_optimise_adaptive(
+            self._p, _ptrs(streams), _ptrs(z), _ptrs(last) if last is not None else None, _ptrs(acc),
+            len(replicas), _ints([r[0] for r in replicas]), _ptrs([r[1] for r in replicas]),
+            _ptrs([r[2] for r in replicas]), _ints([r[3] for r in replicas]), _ints([r[4] for r in replicas]), rate,
+            slot, ctypes.c_float(trust), ctypes.c_float(epsilon), mode, ctypes.c_float(momentum),
+            ctypes.c_float(weight_decay), wpc, first, ctypes.c_uint(flags)),
+            "cbx_ssgd_plan_step_and_optimise_adaptive")
+
     def elastic_step(self, streams: Sequence[int], z: Sequence[int],
                      replicas: Sequence[Tuple[int, int, Optional[int], int]], alpha: float, first: int = 0) -> None:
         """One elastic-averaging barrier (``cbx_ea_plan_step``).  ``replicas[id]``

@@ -164,6 +164,15 @@ class TheGPU:
                                                  ctypes.cast(out.ctypes.data, ctypes.POINTER(_lib.AdaptiveStats)), count))
         return out[:count]
 
+    def base_adaptive_stats(self, device: int, count: int) -> np.ndarray:
+        """``cbx_base_adaptive_stats`` (blocking): the records that
+        ``step_and_synchronise_ssgd_adaptive`` left for the base model's first
+        ``count`` variables on ``device``, shaped like ``replica_adaptive_stats``."""
+        out = np.zeros(max(1, count), dtype=_lib.ADAPTIVE_STATS_FIELDS)
+        check(self._L.cbx_base_adaptive_stats(self._ctx, device,
+                                              ctypes.cast(out.ctypes.data, ctypes.POINTER(_lib.AdaptiveStats)), count))
+        return out[:count]
+
     # ---- solver (SolverConf.GPURegister, SolverConf.java:355-409) ----------
     def setLearningRateDecayPolicyFixed(self, rate: float) -> int:
         return check(self._L.cbx_set_learning_rate_decay_policy_fixed(self._ctx, rate))
@@ -339,6 +348,20 @@ class TheGPU:
         gradient is skipped adds nothing to the base gradient.  Same arguments;
         with clipping off it is that call."""
         return self._step_and_synchronise(self._L.cbx_step_and_synchronise_ssgd_clipped, first, clock, autotune,
+                                          tasks, streams, flags)
+
+    def step_and_synchronise_ssgd_adaptive(self, first: int, clock: int, autotune: int, tasks: Sequence[int],
+                                           streams: Optional[Sequence[Optional[int]]] = None, flags: int = 0) -> int:
+        """``cbx_step_and_synchronise_ssgd_adaptive``:
+        ``step_and_synchronise_ssgd`` with layer-wise adaptive rates on
+        (``set_adaptive_rate``), which that call refuses: one pass accumulates
+        the stepping replicas' steps and takes each variable's norms of the
+        base model and of the mean raw gradient, one wave per variable turns
+        them into the trust ratio, and the apply-and-broadcast kernel scales
+        the accumulated update by it.  ``base_adaptive_stats`` reads the
+        records afterwards.  Same arguments; with the rates off it is that
+        call."""
+        return self._step_and_synchronise(self._L.cbx_step_and_synchronise_ssgd_adaptive, first, clock, autotune,
                                           tasks, streams, flags)
 
     def _step_and_synchronise(self, fn, first, clock, autotune, tasks, streams, flags) -> int:

@@ -658,6 +658,51 @@ int cbx_step_and_synchronise_ssgd (cbx_context *ctx, int first, int clock, int a
  * record.                                                                   */
 int cbx_step_and_synchronise_ssgd_clipped (cbx_context *ctx, int first, int clock, int autotune,
                                            const int *tasks, void *const *streams, unsigned flags);
+/* cbx_step_and_synchronise_ssgd for a context with layer-wise adaptive rates on
+ * (cbx_set_adaptive_rate), which that call and cbx_replica_optimise refuse
+ * under update model WORKER.  An extension: LARS as it was designed for
+ * large-batch synchronous SGD, the trust ratio taken per variable on the base
+ * model z and on the mean of the stepping replicas' gradients, on the device
+ * with no host round trip.  Same arguments.  Three launches on the sync stream
+ * behind the callers' deferred waits (task_ssgd_adaptive_kernels.hip).
+ *
+ * Per element of variable v, one fp32 operation per line:
+ *   acc = the base gradient as found
+ *   Gs  = +0
+ *   per stepping replica i, ascending id:
+ *     Gs  = Gs + g_i                                    raw, before weight decay
+ *     gv  = g_i ; gv = fma (wd, w_i, gv) ; g_i = gv     wd > 0 only; g_i written only with kept outputs
+ *     acc = fma (rate_i, gv, acc)                       cbx_step_and_synchronise_ssgd's sequence
+ *   gbar = ratio * Gs                                   ratio = 1 / wpc
+ *   Z_v = sum z^2, G_v = sum gbar^2 in fp64 from the first add, K_v = the count
+ *         of non-finite floats of both, which add nothing (cbx_set_adaptive_rate's rule 1)
+ *   t_v = cbx_set_adaptive_rate's rule 2 with W = Z_v, G = G_v and beta = the
+ *         stepping replicas' weight decay: 1 for an excluded variable
+ *         (cbx_set_model_variable_adaptive_rate), for one without floats and
+ *         for a degenerate one (Z_v == 0, G_v == 0 or K_v > 0)
+ *   a = t_v * acc
+ *   D = ratio * a ; D = fma (mu, last, D) ; last = D ; z = fma (1, D, z) ; base gradient = +0
+ *   w_j = z for every receiving replica j
+ * The norm is over the mean of the stepping replicas' raw gradients: what the
+ * base gradient held on entry (earlier cbx_replica_optimise calls) joins the
+ * update and not the norm.  Per-variable learning-rate multipliers play no
+ * part, as in both other synchronous-SGD calls.  With t_v == 1 in every
+ * variable the buffers are cbx_step_and_synchronise_ssgd's bit for bit.  The
+ * records (w_sq = Z_v, g_sq = G_v) are the base model's, one set per device:
+ * cbx_base_adaptive_stats.  With the rates off, or nobody stepping, the call is
+ * cbx_step_and_synchronise_ssgd's launch: no norm launch, the records untouched.
+ *
+ * Bytes per element, R replicas stepping and receiving, base momentum on:
+ * (8R + 36) n without weight decay against that call's (8R + 24) n: acc is
+ * written and read again, z is read twice.
+ *
+ * Everything is checked before the first side effect, in
+ * cbx_step_and_synchronise_ssgd's order with its codes.  CBX_ERR_UNSUPPORTED,
+ * naming the call to take, with the rates on and: an update model other than
+ * WORKER, gradient clipping on, more than one device or rank, a model without
+ * variable ranges (registered as raw bytes, or variables that do not tile it). */
+int cbx_step_and_synchronise_ssgd_adaptive (cbx_context *ctx, int first, int clock, int autotune,
+                                            const int *tasks, void *const *streams, unsigned flags);
 /* TheGPU.unlockAny() GPU.c:1142-1149 -> modelmanager.c:233-245           */
 int cbx_unlock_any (cbx_context *ctx);
 
@@ -1007,6 +1052,12 @@ typedef struct cbx_adaptive_stats {
  * (cbx_model_variable_info).  All zeros before the replica's first adaptive
  * step.  count outside [0, variables] is CBX_ERR_INVALID.                   */
 int cbx_replica_adaptive_stats (cbx_context *ctx, int id, cbx_adaptive_stats *out, int count);
+/* Blocking, shaped like cbx_replica_adaptive_stats: drains, then copies the
+ * first `count` variables' records of the base model on device `device` back
+ * (w_sq = Z_v, g_sq = G_v of cbx_step_and_synchronise_ssgd_adaptive).  All
+ * zeros before the first such call with a stepping replica.  count outside
+ * [0, variables] is CBX_ERR_INVALID.                                        */
+int cbx_base_adaptive_stats (cbx_context *ctx, int device, cbx_adaptive_stats *out, int count);
 /* Entries in local device `local`'s table of deferred task-stream waits
  * (see cbx_replica_optimise; at most 64). */
 int cbx_task_wait_count (cbx_context *ctx, int local);
@@ -1753,6 +1804,26 @@ int cbx_ssgd_plan_step_and_optimise_clipped (cbx_sma_plan *plan, void *const *st
                                              const int *locked, const int *step, const float *learning_rate,
                                              const int *slot, float max_norm, int skip_nonfinite, float momentum,
                                              float weight_decay, int wpc, int first, unsigned flags);
+/* cbx_ssgd_plan_step_and_optimise with layer-wise adaptive rates: to a plan
+ * what cbx_step_and_synchronise_ssgd_adaptive is to a context, its arithmetic
+ * and byte counts.  cbx_ssgd_plan_step_and_optimise's arguments plus one slot
+ * and the trust, epsilon and mode of cbx_sma_plan_optimise_adaptive, over a plan
+ * prepared by cbx_sma_plan_set_variables and cbx_sma_plan_set_adaptive
+ * (CBX_ERR_STATE otherwise).  `slot` names the adaptive scratch that takes the
+ * base model's partials, records and trust table; cbx_sma_plan_adaptive_stats
+ * (plan, 0, slot, streams[0], ...) reads the records afterwards.  The three
+ * launches run on streams[0], the last elements ride the third.  The
+ * multipliers of cbx_sma_plan_set_variables play no part; beta is
+ * weight_decay.  CBX_ERR_INVALID, before any launch, for a slot out of range,
+ * a trust or epsilon that is negative, NaN or infinite, a mode other than 0 or
+ * 1.  When nobody steps it is cbx_ssgd_plan_step_and_optimise's launch and the
+ * slot is not touched.                                                      */
+int cbx_ssgd_plan_step_and_optimise_adaptive (cbx_sma_plan *plan, void *const *streams, float *const *z,
+                                              float *const *last, float *const *acc, int nreplicas,
+                                              const int *replica_device, float *const *w, float *const *g,
+                                              const int *locked, const int *step, const float *learning_rate,
+                                              int slot, float trust, float epsilon, int mode, float momentum,
+                                              float weight_decay, int wpc, int first, unsigned flags);
 /* The same seam for the two averaging barriers, over an existing plan: they
  * share its acc / D scratch, communicators, comm stream, per-bucket events
  * and cbx_sma_plan_set_buckets with the SMA and S-SGD steps, so any sequence
